@@ -15,10 +15,19 @@ step   : one pass of the hot path (dg_reconstruct) over one batch of B synthetic
 images (FGSM eps = 0.3 inputs from the bare classifier, model A; built untimed), sharded contiguously over the ranks (gan_defense.shard_range), projected
 in batches, with the single all_gather of (labels, preds, diffs) at the end; images/s = 10 000 / wall ("scaling": "strong").
 
-The timed region carries NO instrumentation.  Per-kernel durations for the roofline leg come from ONE extra, untimed
+A plain run does only what the headline figure needs: set-up, the W warm-up steps, the K timed steps, the outputs
+(--dump-outputs) and the JSON line; its `roofline` holds the whole-path figures only.  --full adds the measurements that take
+runs of their own, after the timed steps: the per-kernel event pass below (`kernels`, the dominant kernel's roofline) and the
+torch-CPU baseline (`cpu_baseline`).
+
+The timed region carries NO instrumentation.  Per-kernel durations for the roofline leg (--full) come from ONE extra, untimed
 step after it, in which every kernel of every GD iteration sits between two hipEvent markers on the launch stream
 (consecutive launches share the marker between them, so the durations add up to that step's wall time,
 `roofline.profiled_step_ms`; the markers themselves make that step ~2 % longer than a timed one).
+
+--dump-outputs DIR: what the last timed step returned to its caller (rec, idx, loss, z; --strong: accuracy, labels, preds,
+diffs), written after the timed steps as DIR/<name>.npy (dump_outputs).  The inputs are drawn from fixed seeds, so two builds
+run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -87,6 +96,28 @@ PROFILE_ROUND = "r06"                  # profiles/<round>_*: the evidence collec
 TRAFFIC_FILE = PROFILE_ROUND + "_pmc_traffic.json"
 TUNING_FILE = PROFILE_ROUND + "_tuning_%s.txt"       # profiles/: the job-list choice of the profiling run, per architecture
 COLL_BACKEND = os.environ.get("DG_BENCH_BACKEND", "nccl")     # "gloo": the shared-GPU test mode of the N > 1 flow (see main)
+DUMP_LIMIT_BYTES = 64 << 20            # --dump-outputs: the most a run writes
+
+
+def dump_outputs(arrays, out_dir, suffix="", limit=DUMP_LIMIT_BYTES):
+    """Writes every named array (torch tensor, NumPy array or scalar) as <out_dir>/<name><suffix>.npy: float64 stays float64,
+    integers and booleans become float64 (exact below 2**53), every other type float32.  When the files would add up to more
+    than `limit` bytes, each array keeps the same fraction of its leading-axis rows, a fixed sample (RandomState(0), rows in order)."""
+    conv = {}
+    for name, v in arrays.items():
+        v = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+        conv[name] = v.astype(np.float64 if v.dtype == np.float64 or v.dtype.kind in "biu" else np.float32)
+    total = sum(v.nbytes for v in conv.values())
+    budget = limit - 4096 * len(conv)                               # room for the .npy headers
+    if total > budget:
+        frac = budget / float(total)
+        for name, v in conv.items():
+            if v.ndim and v.shape[0] > 1:
+                n = max(1, int(v.shape[0] * frac))
+                conv[name] = v[np.sort(np.random.RandomState(0).choice(v.shape[0], n, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in conv.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), v)
 
 
 def make_inputs(gan, a, B, rank=0, first_image=0):
@@ -348,8 +379,13 @@ def main():
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--rec_rr", type=int, default=None)
     ap.add_argument("--rec_iters", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the untimed per-kernel event pass after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the untimed per-kernel event pass (kernels, roofline of the dominant kernel) "
+                         "and the torch-CPU baseline; a plain run does neither")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the untimed per-kernel event pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--strong", action="store_true",
                     help="configs[4] shape: one step = a defended evaluation of --images images sharded over the ranks")
     ap.add_argument("--images", type=int, default=10000, help="--strong: images in the evaluated list")
@@ -363,6 +399,8 @@ def main():
                     help="USE_BN: True variant of the generator (batch-statistics Batchnorm after every hidden layer, "
                          "tflib/ops/batchnorm.py:80-93); not a BASELINE config (the shipped cfgs have USE_BN: False)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     world, rank, local_rank, relaunch = resolve_ranks(args.gpus, os.environ, torch.cuda.device_count())
     if relaunch:
@@ -549,10 +587,19 @@ def main():
         rank_tuning = [bytes(int(v) for v in t[1:].tolist()).hex() for t in allr]
         dt = max(float(t[0].item()) for t in allr)
 
-    # ---- untimed: one more step with every kernel of every GD iteration bracketed by hipEvents (rank 0 reports)
+    # ---- what the last timed step returned to its caller (every rank its own batch; --strong: the gathered evaluation, rank 0)
+    if args.dump_outputs and not (args.strong and rank != 0):
+        if args.strong:
+            arrays = {"accuracy": result["acc"], "labels": result["roc"][0], "preds": result["roc"][1], "diffs": result["roc"][2]}
+        else:
+            arrays = out
+        dump_outputs(arrays, args.dump_outputs, suffix="_rank%d" % rank if rank else "",
+                     limit=DUMP_LIMIT_BYTES // (1 if args.strong else world))
+
+    # ---- untimed (--full): one more step with every kernel of every GD iteration bracketed by hipEvents (rank 0 reports)
     prof = []
     profiled_step_ms = None
-    if not args.no_profile and not args.strong:
+    if args.full and not args.no_profile and not args.strong:
         gan.profile_reset()
         gan.profile_enable(1)
         torch.cuda.synchronize(dev)
@@ -625,7 +672,7 @@ def main():
         else:
             loss = torch.as_tensor(out["loss"]).view(B, R).min(dim=1).values        # NumPy with --host-io
             res["mean_best_loss"] = round(float(loss.mean().item()), 6)
-        if world == 1 and not args.no_cpu_baseline and not args.use_bn:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.use_bn:
             res["cpu_baseline"] = cpu_baseline(arch, params, x[:64].cpu().numpy(), R, L)
         print(json.dumps(res), flush=True)
     if distributed:

@@ -281,3 +281,28 @@ def test_cpu_baseline_follows_the_fixed_rule():
     assert 0.0 <= r["spread"] and "fixed rule" in r["sample"] and "two batches" in r["sample"]
     if old is not None:
         assert set(os.sched_getaffinity(0)) == old                      # the pinning is undone
+
+
+def test_dump_outputs_types_and_size_cap(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32 / float64 (integers exact in float64); past the size cap each array
+    keeps the same fixed sample of its rows, so that two runs of one build write the same files."""
+    import numpy as np
+    import torch
+    rs = np.random.RandomState(1)
+    arrays = {"rec": torch.from_numpy(rs.rand(40, 5, 5).astype(np.float32)), "idx": np.arange(40, dtype=np.int64) * 3,
+              "loss": rs.rand(400), "accuracy": 0.25}
+    bench.dump_outputs(arrays, str(tmp_path / "a"))
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in arrays}
+    assert got["rec"].dtype == np.float32 and np.array_equal(got["rec"], arrays["rec"].numpy())
+    assert got["idx"].dtype == np.float64 and np.array_equal(got["idx"], np.arange(40) * 3)
+    assert got["loss"].dtype == np.float64 and got["accuracy"].shape == () and float(got["accuracy"]) == 0.25
+    limit = 4096 * len(arrays) + 3000                                    # room for 3000 of the 7528 bytes
+    for d in ("b", "c"):
+        bench.dump_outputs(arrays, str(tmp_path / d), limit=limit)
+    files = sorted(os.listdir(str(tmp_path / "b")))
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in files) <= limit
+    for f in files:
+        b, c = np.load(str(tmp_path / "b" / f)), np.load(str(tmp_path / "c" / f))
+        assert np.array_equal(b, c)
+    sub = np.load(str(tmp_path / "b" / "idx.npy"))
+    assert 0 < len(sub) < 40 and np.all(np.diff(sub) > 0) and np.isin(sub, np.arange(40) * 3).all()

@@ -75,10 +75,10 @@ def test_sharded_evaluation_over_rccl_equals_the_unsharded_call():
 
 @pytest.mark.parametrize("extra", [[], ["--strong", "--images", "230", "--batch", "100"]])
 def test_bench_runs_its_rccl_path_with_one_rank(extra):
-    """bench.py under DG_BENCH_FORCE_DIST=1: process group over nccl, barrier + all_gather / the sharded evaluation inside
-    the timed region, ONE JSON line with the contract's keys."""
+    """bench.py --full under DG_BENCH_FORCE_DIST=1: process group over nccl, barrier + all_gather / the sharded evaluation inside
+    the timed region, the per-kernel event pass after it, ONE JSON line with the contract's keys."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--rec_iters", "4",
-           "--no-cpu-baseline"] + extra
+           "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, env=_env(DG_BENCH_FORCE_DIST="1"), cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -97,15 +97,16 @@ def test_bench_runs_its_rccl_path_with_one_rank(extra):
 
 
 @pytest.mark.parametrize("extra", [[], ["--strong", "--images", "230", "--batch", "100"]])
-def test_bench_two_rank_flow_on_one_gpu_over_gloo(extra):
+def test_bench_two_rank_flow_on_one_gpu_over_gloo(extra, tmp_path):
     """The driver's N > 1 command line -- torch.distributed.run starting two ranks of bench.py --gpus 2 -- on the one GPU of a test
     box: DG_BENCH_BACKEND=gloo moves the control tensors of the collectives to the CPU (RCCL refuses two ranks on one device),
     everything else is the code an 8-GPU run executes: rank 0 installs / times the job lists and broadcasts them, rank 1 imports
     them, barrier, the timed steps on two engines, the gather, the max over ranks, ONE line from rank 0.  The line says what it is
-    (n_gpus = 1) and carries both ranks' times and job-list ids."""
+    (n_gpus = 1) and carries both ranks' times and job-list ids; --dump-outputs writes each rank's batch (--strong: the gathered
+    evaluation, once)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--rec_iters", "4", "--no-cpu-baseline"] + extra
+           "--rec_iters", "4", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)] + extra
     env = dict(os.environ)
     env.update({"DG_BENCH_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -121,6 +122,12 @@ def test_bench_two_rank_flow_on_one_gpu_over_gloo(extra):
     assert res["config"]["parallelism"] == "shard2"
     if extra:
         assert res["scaling"] == "strong" and 0.0 <= res["accuracy"] <= 1.0
+        assert sorted(os.listdir(str(tmp_path))) == ["accuracy.npy", "diffs.npy", "labels.npy", "preds.npy"]
+        assert np.load(str(tmp_path / "preds.npy")).shape == (230,)
+        assert float(np.load(str(tmp_path / "accuracy.npy"))) == pytest.approx(res["accuracy"], abs=1e-4)
+    else:
+        names = sorted(os.listdir(str(tmp_path)))
+        assert names == sorted(n + s + ".npy" for n in ("rec", "idx", "loss", "z") for s in ("", "_rank1")), names
 
 
 _WORKER2 = r"""

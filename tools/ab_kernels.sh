@@ -8,7 +8,7 @@ cp $LIB /tmp/dg_new.so
 for round in 1 2; do
   for v in new other; do
     if [ $v = new ]; then cp /tmp/dg_new.so $LIB; else cp $OTHER $LIB; fi
-    python bench.py --no-cpu-baseline --steps 8 --warmup 2 "$@" > $O/ab_${v}_$round.json 2> $O/ab_${v}_$round.err
+    python bench.py --full --no-cpu-baseline --steps 8 --warmup 2 "$@" > $O/ab_${v}_$round.json 2> $O/ab_${v}_$round.err
   done
 done
 cp /tmp/dg_new.so $LIB

@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 BUILD=$(python -c "import bench; print(bench.build_id())")
 echo "build $BUILD" > $OUT/build_celeba.txt
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o celeba -- python bench.py --workload celeba --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_celeba_under_rocprof.json 2> $OUT/stats_celeba.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o celeba -- python bench.py --full --workload celeba --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_celeba_under_rocprof.json 2> $OUT/stats_celeba.err
 find $OUT/stats -name "celeba_kernel_stats.csv" -exec cp {} $OUT/ \;
 python -c "import json; d=json.load(open('$OUT/bench_celeba_under_rocprof.json')); print(d['value'], d['roofline']['frac'], d['roofline']['path_frac'], [(k['name'],k['avg_us']) for k in d['kernels']])"
 CMD="python bench.py --workload celeba --steps 1 --warmup 1 --rec_iters 4 --no-cpu-baseline --no-profile"

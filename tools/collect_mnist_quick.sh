@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 BUILD=$(python -c "import bench; print(bench.build_id())")
 echo "build $BUILD" > $OUT/build.txt
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o mnist -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_mnist_under_rocprof.json 2> $OUT/stats_mnist.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o mnist -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_mnist_under_rocprof.json 2> $OUT/stats_mnist.err
 find $OUT/stats -name "*kernel_stats.csv" -exec cp {} $OUT/ \;
 python -c "import json; d=json.load(open('$OUT/bench_mnist_under_rocprof.json')); print(d['value'], d['roofline']['frac'], d['roofline']['path_frac'], [(k['name'],k['avg_us']) for k in d['kernels']])"
 CMD="python bench.py --workload mnist --steps 1 --warmup 1 --rec_iters 4 --no-cpu-baseline --no-profile"

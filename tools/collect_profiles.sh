@@ -14,11 +14,11 @@ BUILD=$(python -c "import bench; print(bench.build_id())")
 echo "build $BUILD" > $OUT/build.txt
 tid() { python -c "import sys; from defensegan_amd.gan import tuning_text_id; print(tuning_text_id(open(sys.argv[1]).read()))" $1; }
 export DG_TUNING_CACHE=$PWD/$OUT/tuning_mnist.txt
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_mnist_driver_cmd.json 2> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o mnist -- python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_mnist_under_rocprof.json 2> $OUT/stats_mnist.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_mnist_driver_cmd.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o mnist -- python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_mnist_under_rocprof.json 2> $OUT/stats_mnist.err
 export DG_TUNING_CACHE=$PWD/$OUT/tuning_celeba.txt
-python bench.py --workload celeba --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_celeba.json 2>> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o celeba -- python bench.py --workload celeba --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_celeba_under_rocprof.json 2> $OUT/stats_celeba.err
+python bench.py --full --workload celeba --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_celeba.json 2>> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o celeba -- python bench.py --full --workload celeba --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_celeba_under_rocprof.json 2> $OUT/stats_celeba.err
 for W in mnist celeba; do
   export DG_TUNING_CACHE=$PWD/$OUT/tuning_$W.txt
   CMD="python bench.py --workload $W --steps 1 --warmup 1 --rec_iters 4 --no-cpu-baseline --no-profile"

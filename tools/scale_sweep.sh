@@ -18,7 +18,7 @@ if [ "$HAVE" -lt "$MAXN" ]; then
 fi
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 for n in $NS; do
-  python bench.py --gpus $n --steps ${STEPS:-10} --warmup ${WARMUP:-3} --no-cpu-baseline > $O/weak_$n.json 2> $O/weak_$n.err || { echo "weak N=$n failed"; tail -3 $O/weak_$n.err; }
+  python bench.py --full --gpus $n --steps ${STEPS:-10} --warmup ${WARMUP:-3} --no-cpu-baseline > $O/weak_$n.json 2> $O/weak_$n.err || { echo "weak N=$n failed"; tail -3 $O/weak_$n.err; }
   python bench.py --gpus $n --strong --steps 1 --warmup 0 --no-cpu-baseline > $O/strong_$n.json 2> $O/strong_$n.err || { echo "strong N=$n failed"; tail -3 $O/strong_$n.err; }
 done
 python - $O $NS <<'PY' | tee $O/summary.txt
