@@ -240,6 +240,9 @@ __global__ __launch_bounds__(256) void clf_fgsm_kernel(const float* __restrict__
 
 }  // namespace
 
+struct CwWork;
+extern "C" __attribute__((visibility("hidden"))) void dg_cw_release(CwWork* w);     // dg_cw.hip
+
 struct dg_clf {
     int device = 0;
     int in_h = 0, in_w = 0, in_c = 0;
@@ -256,6 +259,7 @@ struct dg_clf {
     size_t gbuf_floats = 0;
     size_t scores_floats = 0;
     int n_out = 0;
+    CwWork* cw = nullptr;                     // Carlini-Wagner workspace (dg_cw.hip), grown on demand
 };
 
 extern "C" {
@@ -288,6 +292,7 @@ int dg_clf_destroy(dg_clf* h) {
         if (p) (void)hipFree(p);
     for (float* p : h->gbuf)
         if (p) (void)hipFree(p);
+    dg_cw_release(h->cw);
     delete h;
     return DG_OK;
 }
@@ -470,10 +475,14 @@ int dg_eval_batch(dg_clf* h, const float* rec, const float* orig, const int32_t*
     return DG_OK;
 }
 
-// d(sum_b CE(softmax(logits_b), y_b))/dx for x [B,H,W,C]; y = labels or, when NULL, the model's own prediction.
-static int clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float** grad_out, hipStream_t s) {
-    int rc = clf_run(h, x, B, nullptr, nullptr, s, /*keep=*/true);
-    if (rc) return rc;
+static int clf_last_layer(const dg_clf* h) {
+    int last = -1;
+    for (int j = 0; j < (int)h->layers.size(); ++j)
+        if (!h->layers[j].skip && h->layers[j].kind != L_SOFTMAX) last = j;
+    return last;
+}
+
+static int clf_grow_gbuf(dg_clf* h, int B) {
     size_t need = (size_t)B * h->in_h * h->in_w * h->in_c;
     for (const auto& l : h->layers) need = std::max(need, (size_t)B * l.oh * l.ow * l.oc);
     if (need > h->gbuf_floats) {
@@ -484,13 +493,15 @@ static int clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, 
         }
         h->gbuf_floats = need;
     }
-    int last = -1;
-    for (int j = 0; j < (int)h->layers.size(); ++j)
-        if (!h->layers[j].skip && h->layers[j].kind != L_SOFTMAX) last = j;
-    const int n = h->layers[last].oh * h->layers[last].ow * h->layers[last].oc;
+    return DG_OK;
+}
+
+// The seed-agnostic chain: g = seed [B, n] = dLoss/dlogits -> dLoss/dx, through the layer outputs the last
+// clf_run(keep = true) left in h->acts.  The result lies in one of the gbuf ping-pong buffers (never in `seed`).
+static int clf_backward_chain(dg_clf* h, const float* seed, int B, float** grad_out, hipStream_t s) {
+    const int last = clf_last_layer(h);
     int which = 0;
-    float* g = h->gbuf[which];
-    hipLaunchKernelGGL(clf_ce_grad_kernel, dim3((B + 63) / 64), dim3(64), 0, s, h->acts[last], labels, g, B, n);
+    const float* g = seed;
     for (int j = last; j >= 0; --j) {
         const ClfLayer& l = h->layers[j];
         if (l.skip || l.kind == L_SOFTMAX) continue;
@@ -509,8 +520,46 @@ static int clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, 
         g = dx;
     }
     CLF_TRY(hipGetLastError());
-    *grad_out = g;
+    *grad_out = const_cast<float*>(g);
     return DG_OK;
+}
+
+// d(sum_b CE(softmax(logits_b), y_b))/dx for x [B,H,W,C]; y = labels or, when NULL, the model's own prediction.
+static int clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float** grad_out, hipStream_t s) {
+    int rc = clf_run(h, x, B, nullptr, nullptr, s, /*keep=*/true);
+    if (rc) return rc;
+    if ((rc = clf_grow_gbuf(h, B))) return rc;
+    const int last = clf_last_layer(h);
+    const int n = h->layers[last].oh * h->layers[last].ow * h->layers[last].oc;
+    float* g = h->gbuf[0];
+    hipLaunchKernelGGL(clf_ce_grad_kernel, dim3((B + 63) / 64), dim3(64), 0, s, h->acts[last], labels, g, B, n);
+    return clf_backward_chain(h, g, B, grad_out, s);
+}
+
+// ---- library-internal entries of the Carlini-Wagner attack (dg_cw.hip) ------------------------------------------------
+// Forward of x [B, ...] keeping every layer's output; *logits = the kept logits [B, n] (valid until the next clf_run).
+__attribute__((visibility("hidden"))) int dg_clf_kept_forward(dg_clf* h, const float* x, int B, hipStream_t s,
+                                                              const float** logits) {
+    int rc = clf_run(h, x, B, nullptr, nullptr, s, /*keep=*/true);
+    if (rc) return rc;
+    *logits = h->acts[clf_last_layer(h)];
+    return DG_OK;
+}
+
+// dLoss/dx from the seed dLoss/dlogits [B, n] after dg_clf_kept_forward of the same B images.
+__attribute__((visibility("hidden"))) int dg_clf_seeded_backward(dg_clf* h, const float* seed, int B, hipStream_t s, float** grad) {
+    int rc = clf_grow_gbuf(h, B);
+    if (rc) return rc;
+    return clf_backward_chain(h, seed, B, grad, s);
+}
+
+// device, pixels per image, class count (0 before the model is complete) and the CW workspace slot
+__attribute__((visibility("hidden"))) CwWork** dg_clf_cw_slot(dg_clf* h, int* device, int* P, int* n) {
+    *device = h->device;
+    *P = h->in_h * h->in_w * h->in_c;
+    const int last = clf_last_layer(h);
+    *n = last < 0 ? 0 : h->layers[last].oh * h->layers[last].ow * h->layers[last].oc;
+    return &h->cw;
 }
 
 int dg_clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float* grad, void* stream) {
@@ -520,6 +569,19 @@ int dg_clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, int 
     int rc = clf_input_gradient(h, x, labels, B, &g, (hipStream_t)stream);
     if (rc) return rc;
     CLF_TRY(hipMemcpyAsync(grad, g, (size_t)B * h->in_h * h->in_w * h->in_c * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DG_OK;
+}
+
+int dg_clf_backward(dg_clf* h, const float* x, const float* dlogits, int B, float* grad, void* stream) {
+    if (!h || !x || !dlogits || !grad || B <= 0) return fail(DG_E_INVALID, "dg_clf_backward: bad argument");
+    CLF_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = clf_run(h, x, B, nullptr, nullptr, s, /*keep=*/true);
+    if (rc) return rc;
+    if ((rc = clf_grow_gbuf(h, B))) return rc;
+    float* g = nullptr;
+    if ((rc = clf_backward_chain(h, dlogits, B, &g, s))) return rc;
+    CLF_TRY(hipMemcpyAsync(grad, g, (size_t)B * h->in_h * h->in_w * h->in_c * sizeof(float), hipMemcpyDeviceToDevice, s));
     return DG_OK;
 }
 

@@ -1,0 +1,395 @@
+// The third white-box attack of the reference (whitebox.py:192-210, --attack_type cw): cleverhans' CarliniWagnerL2, run as
+// ONE asynchronous device call (dg_cw in include/defensegan_hip.h).  cleverhans is an empty, un-pinned submodule of the
+// reference; its published attack (cleverhans 2.x attacks_tf.py, after Carlini's nn_robust_attacks) is restated.  Per image,
+// lo / hi = clip_min / clip_max, P pixels, Z = logits (the layer before Softmax), t = label (y, y_target or the model's own
+// first argmax on x):
+//
+//   setup        oimg = clip(x, lo, hi);  timg = atanh((clip((x - lo) / (hi - lo), 0, 1) * 2 - 1) * 0.999999)
+//                other = (tanh(timg) + 1) / 2 * (hi - lo) + lo;  x_adv = oimg, o_bestl2 = 1e10, o_bestscore = -1, const = c0
+//   outer step   (binary_search_steps) w = m = v = 0, bestl2 = 1e10, bestscore = -1, chunk prev = 1e6;
+//                const = upper_bound on the last step when binary_search_steps >= 10 ("repeat")
+//   iteration i  values from the PRE-update w (what sess.run([train, loss, l2dist, output, newimg]) returns):
+//                newimg = (tanh(w + timg) + 1) / 2 * (hi - lo) + lo,  l2 = sum (newimg - other)^2
+//                real = Z_t,  oth = max_k((1 - [k=t]) Z_k - [k=t] 10000)
+//                loss1 = const * max(0, real - oth + kappa)   (targeted: max(0, oth - real + kappa))
+//                dloss1/dZ only where the max argument is > 0 (TF Maximum sends ties to the constant 0), the max's share split
+//                evenly over its maximisers (TF _MaxGrad), the label's own entry takes none of it
+//                g = (dloss1/dnewimg + 2 (newimg - other)) * (hi - lo) / 2 * (1 - tanh^2(w + timg))
+//                TF Adam (beta1 0.9, beta2 0.999, eps 1e-8, step = i + 1): m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2,
+//                w -= lr sqrt(1 - b2^step) / (1 - b1^step) * m / (sqrt(v) + eps)
+//                abort early on i % max(max_iterations / 10, 1) == 0: the CHUNK's L = sum (loss1 + l2) > prev * 0.9999 stops
+//                the chunk (that iteration's Adam step happened, its best tracking does not); otherwise prev = L
+//                success = first argmax(Z') != t (targeted: == t), Z'_t = Z_t + kappa (targeted: Z_t - kappa);
+//                l2 < bestl2 and success: bestl2 = l2, bestscore = argmax Z; l2 < o_bestl2 and success: the same for
+//                o_bestl2 / o_bestscore, and x_adv = newimg
+//   after step   bestscore != -1 and it counts as success: upper = min(upper, const), else lower = max(lower, const);
+//                const = (lower + upper) / 2 if upper < 1e9, else (failure branch only) const *= 10
+//
+// Chunks of batch_size images share L and the abort decision; nothing else couples images.  A trailing partial chunk is a chunk
+// of its own (cleverhans cannot run one).  Documented differences: L is summed in float64 in a fixed order (TF: float32
+// reduce_sum), the constants are float64 and enter the loss as float32 (as the fed placeholder does), ties in the model's own
+// prediction go to the first class (cleverhans splits them evenly).
+//
+// Per iteration the call enqueues: the classifier forward over all N images, keeping activations (dg_clf.hip, unchanged); (a)
+// cw_head_kernel, one workgroup per image: l2, real / oth / loss1, the logit seed, success and argmax; the seeded backward to the
+// input (dg_clf.hip's chain, unchanged); (b) cw_chunk_kernel, one workgroup per chunk: L in a fixed order (no float atomics:
+// deterministic, and a chunk's images give the same bits alone or inside a larger call), the abort decision, best tracking,
+// an "improved" flag per image; (c) cw_update_kernel, elementwise: x_adv = newimg where improved, the tanh / L2 gradient, Adam,
+// the next w and newimg.  (d) cw_reset_kernel runs once per outer step: the constant update of the step before, the resets.
+// No host synchronisation, copy or decision inside the call, and no graph capture (include/defensegan_hip.h, graph_max_rows).
+//
+// Deviation from "aborted chunks cost nothing": (a), (b) and (c) return at once for a chunk that has stopped, but the classifier
+// kernels are FGSM's, untouched by this attack (bit-identity of dg_clf_input_gradient / dg_fgsm), and know no chunks; they
+// keep running over all N images.  tools/cw_time.py measures abort_early on and off.  gfx950 only.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+
+#include "../../include/defensegan_hip.h"
+
+struct CwWork;
+extern "C" {
+__attribute__((visibility("hidden"))) void dg_set_error_message(const char* msg);    // dg_engine.cpp
+__attribute__((visibility("hidden"))) int dg_clf_kept_forward(dg_clf* h, const float* x, int B, hipStream_t s, const float** logits);
+__attribute__((visibility("hidden"))) int dg_clf_seeded_backward(dg_clf* h, const float* seed, int B, hipStream_t s, float** grad);
+__attribute__((visibility("hidden"))) CwWork** dg_clf_cw_slot(dg_clf* h, int* device, int* P, int* n);
+}
+
+struct CwWork {
+    void* mem = nullptr;
+    size_t bytes = 0;
+};
+
+namespace {
+
+int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    dg_set_error_message(buf);
+    return code;
+}
+
+#define CW_TRY(expr)                                                                                \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess) return fail(DG_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));        \
+    } while (0)
+
+// the workspace, carved from one allocation: N x P planes, the seed, per-image and per-chunk scalars
+struct CwBufs {
+    float *w, *m, *v, *timg, *other, *newimg;      // [N, P]
+    float* seed;                                   // [N, n] dloss1/dlogits
+    float *l2, *loss1, *bestl2, *obestl2;          // [N]
+    double *cst, *lower, *upper;                   // [N]
+    int32_t *lab, *score, *succ, *bestscore, *obestscore, *improved;   // [N]
+    double* prev;                                  // [chunks]
+    int32_t* abort_iter;                           // [chunks]: -1 running, else the iteration whose check stopped the chunk
+};
+
+size_t carve(CwBufs* b, char* base, long long N, long long P, long long n, long long chunks) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) -> char* {
+        char* p = base ? base + off : nullptr;
+        off += (bytes + 255) & ~(size_t)255;
+        return p;
+    };
+    const size_t plane = (size_t)(N * P) * sizeof(float);
+    b->w = (float*)take(plane); b->m = (float*)take(plane); b->v = (float*)take(plane);
+    b->timg = (float*)take(plane); b->other = (float*)take(plane); b->newimg = (float*)take(plane);
+    b->seed = (float*)take((size_t)(N * n) * sizeof(float));
+    b->l2 = (float*)take(N * sizeof(float)); b->loss1 = (float*)take(N * sizeof(float));
+    b->bestl2 = (float*)take(N * sizeof(float)); b->obestl2 = (float*)take(N * sizeof(float));
+    b->cst = (double*)take(N * sizeof(double)); b->lower = (double*)take(N * sizeof(double)); b->upper = (double*)take(N * sizeof(double));
+    b->lab = (int32_t*)take(N * 4); b->score = (int32_t*)take(N * 4); b->succ = (int32_t*)take(N * 4);
+    b->bestscore = (int32_t*)take(N * 4); b->obestscore = (int32_t*)take(N * 4); b->improved = (int32_t*)take(N * 4);
+    b->prev = (double*)take(chunks * sizeof(double));
+    b->abort_iter = (int32_t*)take(chunks * 4);
+    return off;
+}
+
+__device__ __forceinline__ float cw_to_img(float t, float lo, float hi) { return (t + 1.0f) * 0.5f * (hi - lo) + lo; }
+
+__device__ __forceinline__ int first_argmax(const float* z, int n) {
+    int best = 0;
+    for (int k = 1; k < n; ++k)
+        if (z[k] > z[best]) best = k;
+    return best;
+}
+
+// once per call, one workgroup per image: the label, timg, other, x_adv = clip(x), the per-image constants and outer bests
+__global__ __launch_bounds__(256) void cw_setup_kernel(const float* __restrict__ x, const int32_t* __restrict__ labels,
+                                                        const float* __restrict__ logits, int n, long long P, float lo, float hi,
+                                                        double initial_const, CwBufs bf, float* __restrict__ xadv) {
+    const long long b = blockIdx.x;
+    if (threadIdx.x == 0) {
+        bf.lab[b] = labels ? labels[b] : first_argmax(logits + b * n, n);
+        bf.obestl2[b] = 1e10f;
+        bf.obestscore[b] = -1;
+        bf.cst[b] = initial_const;
+        bf.lower[b] = 0.0;
+        bf.upper[b] = 1e10;
+    }
+    const float* xb = x + b * P;
+    for (long long i = threadIdx.x; i < P; i += 256) {
+        const float xv = xb[i];
+        float u = (xv - lo) / (hi - lo);
+        u = u < 0.f ? 0.f : (u > 1.f ? 1.f : u);
+        const float ti = atanhf((u * 2.0f - 1.0f) * 0.999999f);
+        bf.timg[b * P + i] = ti;
+        bf.other[b * P + i] = cw_to_img(tanhf(ti), lo, hi);
+        xadv[b * P + i] = xv < lo ? lo : (xv > hi ? hi : xv);
+    }
+}
+
+// (d) once per outer step, one workgroup per image: the constant update of the previous step (update != 0), the repeat rule,
+// and the resets of w, m, v, newimg, the step's bests and the chunk's abort state (reset != 0; reset == 0 after the last step:
+// the constant update alone, so that the constants returned are cleverhans' final ones)
+__global__ __launch_bounds__(256) void cw_reset_kernel(CwBufs bf, long long P, int batch_size, int update, int reset, int repeat_last,
+                                                        int targeted, float lo, float hi) {
+    const long long b = blockIdx.x;
+    if (threadIdx.x == 0) {
+        if (update) {
+            const int bs = bf.bestscore[b], t = bf.lab[b];
+            const double c = bf.cst[b];
+            if (bs != -1 && (targeted ? bs == t : bs != t)) {
+                bf.upper[b] = fmin(bf.upper[b], c);
+                if (bf.upper[b] < 1e9) bf.cst[b] = (bf.lower[b] + bf.upper[b]) / 2;
+            } else {
+                bf.lower[b] = fmax(bf.lower[b], c);
+                bf.cst[b] = bf.upper[b] < 1e9 ? (bf.lower[b] + bf.upper[b]) / 2 : c * 10;
+            }
+        }
+        if (!reset) return;
+        if (repeat_last) bf.cst[b] = bf.upper[b];
+        bf.bestl2[b] = 1e10f;
+        bf.bestscore[b] = -1;
+        if (b % batch_size == 0) {
+            bf.prev[b / batch_size] = 1e6;
+            bf.abort_iter[b / batch_size] = -1;
+        }
+    }
+    if (!reset) return;
+    for (long long i = threadIdx.x; i < P; i += 256) {
+        const long long j = b * P + i;
+        bf.w[j] = 0.f;
+        bf.m[j] = 0.f;
+        bf.v[j] = 0.f;
+        bf.newimg[j] = cw_to_img(tanhf(0.f + bf.timg[j]), lo, hi);
+    }
+}
+
+// (a) one workgroup per image: l2 (fixed-order block reduction), loss1, the seed dloss1/dZ, success and argmax
+__global__ __launch_bounds__(256) void cw_head_kernel(const float* __restrict__ logits, int n, long long P, int batch_size, int targeted,
+                                                       float confidence, CwBufs bf) {
+    __shared__ float red[4];
+    const long long b = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* sd = bf.seed + b * n;
+    if (bf.abort_iter[b / batch_size] >= 0) {          // stopped chunk: a zero seed, nothing else
+        for (int k = tid; k < n; k += 256) sd[k] = 0.f;
+        return;
+    }
+    const float* ni = bf.newimg + b * P;
+    const float* ot = bf.other + b * P;
+    float sq = 0.f;
+    for (long long i = tid; i < P; i += 256) {
+        const float d = ni[i] - ot[i];
+        sq = __builtin_fmaf(d, d, sq);
+    }
+#pragma unroll
+    for (int msk = 32; msk >= 1; msk >>= 1) sq += __shfl_xor(sq, msk, 64);
+    if (lane == 0) red[wave] = sq;
+    __syncthreads();
+    if (tid != 0) return;
+    const float l2 = (red[0] + red[1]) + (red[2] + red[3]);
+    const float* z = logits + b * n;
+    const int t = bf.lab[b];
+    if (t < 0 || t >= n) {                             // a label outside the classes: never a success, no gradient
+        for (int k = 0; k < n; ++k) sd[k] = 0.f;
+        bf.l2[b] = l2;
+        bf.loss1[b] = 0.f;
+        bf.succ[b] = 0;
+        bf.score[b] = first_argmax(z, n);
+        return;
+    }
+    const float real = z[t];
+    float oth = -3.402823466e38f;
+    for (int k = 0; k < n; ++k) {
+        const float o = k == t ? -10000.0f : z[k];
+        oth = o > oth ? o : oth;
+    }
+    int cnt = 0;
+    for (int k = 0; k < n; ++k) cnt += ((k == t ? -10000.0f : z[k]) == oth) ? 1 : 0;
+    const float c = (float)bf.cst[b];
+    const float arg = targeted ? (oth - real + confidence) : (real - oth + confidence);
+    const float loss1 = c * (arg > 0.f ? arg : 0.f);
+    for (int k = 0; k < n; ++k) sd[k] = 0.f;
+    if (arg > 0.f) {
+        const float sgn = targeted ? -1.0f : 1.0f;
+        const float share = (1.0f / (float)cnt) * (-sgn * c);
+        for (int k = 0; k < n; ++k)
+            if (k != t && z[k] == oth) sd[k] = share;
+        sd[t] = sgn * c;
+    }
+    // success on Z' (label entry moved by the confidence), the recorded score on Z itself
+    int am = 0;
+    float best = t == 0 ? (targeted ? z[0] - confidence : z[0] + confidence) : z[0];
+    for (int k = 1; k < n; ++k) {
+        const float zk = k == t ? (targeted ? z[k] - confidence : z[k] + confidence) : z[k];
+        if (zk > best) { best = zk; am = k; }
+    }
+    bf.l2[b] = l2;
+    bf.loss1[b] = loss1;
+    bf.succ[b] = targeted ? (am == t) : (am != t);
+    bf.score[b] = first_argmax(z, n);
+}
+
+// (b) one workgroup per chunk: the chunk's loss in a fixed order, the abort decision on check iterations, best tracking
+__global__ __launch_bounds__(256) void cw_chunk_kernel(CwBufs bf, int N, int batch_size, int iter, int check) {
+    __shared__ int abort_now, stopped;
+    const int c = blockIdx.x;
+    const int first = c * batch_size;
+    const int cnt = N - first < batch_size ? N - first : batch_size;
+    // thread 0 alone reads and writes the chunk's abort state; the others learn it after the barrier (a read of abort_iter by
+    // another wave could otherwise see this iteration's write and skip the "improved" flags the update kernel still reads)
+    if (threadIdx.x == 0) {
+        stopped = bf.abort_iter[c] >= 0;
+        abort_now = 0;
+        if (!stopped && check) {
+            double L = 0.0;
+            for (int j = 0; j < cnt; ++j) L += (double)bf.loss1[first + j] + (double)bf.l2[first + j];
+            if (L > bf.prev[c] * 0.9999) {
+                bf.abort_iter[c] = iter;
+                abort_now = 1;
+            } else {
+                bf.prev[c] = L;
+            }
+        }
+    }
+    __syncthreads();
+    if (stopped) return;
+    for (int j = threadIdx.x; j < cnt; j += 256) {
+        const int b = first + j;
+        int imp = 0;
+        if (!abort_now && bf.succ[b]) {
+            const float l2 = bf.l2[b];
+            if (l2 < bf.bestl2[b]) {
+                bf.bestl2[b] = l2;
+                bf.bestscore[b] = bf.score[b];
+            }
+            if (l2 < bf.obestl2[b]) {
+                bf.obestl2[b] = l2;
+                bf.obestscore[b] = bf.score[b];
+                imp = 1;
+            }
+        }
+        bf.improved[b] = imp;
+    }
+}
+
+// (c) elementwise: x_adv = newimg where the image improved, then the gradient through tanh, TF Adam, the next w and newimg
+__global__ __launch_bounds__(256) void cw_update_kernel(CwBufs bf, const float* __restrict__ grad, float* __restrict__ xadv, long long total,
+                                                         long long P, int batch_size, int iter, float lr_t, float lo, float hi) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long long b = i / P;
+    const int ai = bf.abort_iter[b / batch_size];
+    if (ai >= 0 && ai != iter) return;
+    const float ni = bf.newimg[i];
+    if (bf.improved[b]) xadv[i] = ni;
+    const float ti = bf.timg[i];
+    const float w = bf.w[i];
+    const float th = tanhf(w + ti);
+    const float g = (grad[i] + 2.0f * (ni - bf.other[i])) * ((hi - lo) * 0.5f * (1.0f - th * th));
+    const float m = 0.9f * bf.m[i] + 0.1f * g;
+    const float v = 0.999f * bf.v[i] + 0.001f * (g * g);
+    const float wn = w - lr_t * m / (sqrtf(v) + 1e-8f);
+    bf.m[i] = m;
+    bf.v[i] = v;
+    bf.w[i] = wn;
+    bf.newimg[i] = cw_to_img(tanhf(wn + ti), lo, hi);
+}
+
+}  // namespace
+
+extern "C" {
+
+__attribute__((visibility("hidden"))) void dg_cw_release(CwWork* w) {
+    if (!w) return;
+    if (w->mem) (void)hipFree(w->mem);
+    delete w;
+}
+
+int dg_cw(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted, int batch_size, float confidence, float learning_rate,
+          int binary_search_steps, int max_iterations, int abort_early, double initial_const, float clip_min, float clip_max,
+          float* x_adv, float* best_l2, int32_t* best_class, double* final_const, int32_t* chunk_stop, void* stream) {
+    if (!h || !x || !x_adv || B <= 0) return fail(DG_E_INVALID, "dg_cw: bad argument");
+    if (batch_size <= 0 || binary_search_steps < 0 || max_iterations < 0 || !(clip_max > clip_min))
+        return fail(DG_E_INVALID, "dg_cw: bad parameters (batch_size %d, binary_search_steps %d, max_iterations %d, clip [%g, %g])",
+                    batch_size, binary_search_steps, max_iterations, (double)clip_min, (double)clip_max);
+    int device = 0, Pi = 0, n = 0;
+    CwWork** slot = dg_clf_cw_slot(h, &device, &Pi, &n);
+    if (n <= 0) return fail(DG_E_STATE, "dg_cw: classifier has no layers");
+    CW_TRY(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    const long long N = B, P = Pi, chunks = (N + batch_size - 1) / batch_size;
+    CwBufs bf;
+    const size_t need = carve(&bf, nullptr, N, P, n, chunks);
+    if (!*slot) *slot = new CwWork();
+    CwWork* wk = *slot;
+    if (need > wk->bytes) {
+        if (wk->mem) (void)hipFree(wk->mem);
+        wk->mem = nullptr;
+        wk->bytes = 0;
+        CW_TRY(hipMalloc(&wk->mem, need));
+        wk->bytes = need;
+    }
+    carve(&bf, (char*)wk->mem, N, P, n, chunks);
+
+    const float lo = clip_min, hi = clip_max;
+    const float* logits = nullptr;
+    int rc = DG_OK;
+    if (!labels && (rc = dg_clf_kept_forward(h, x, B, s, &logits))) return rc;      // the model's own prediction on x
+    hipLaunchKernelGGL(cw_setup_kernel, dim3((unsigned)N), dim3(256), 0, s, x, labels, labels ? nullptr : logits, n, P, lo, hi,
+                       initial_const, bf, x_adv);
+    CW_TRY(hipGetLastError());
+    const long long total = N * P;
+    const unsigned egrid = (unsigned)((total + 255) / 256);
+    const int every = max_iterations / 10 > 0 ? max_iterations / 10 : 1;
+    for (int step = 0; step < binary_search_steps; ++step) {
+        const int repeat_last = (binary_search_steps >= 10 && step == binary_search_steps - 1) ? 1 : 0;
+        hipLaunchKernelGGL(cw_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, P, batch_size, step > 0 ? 1 : 0, 1, repeat_last,
+                           targeted ? 1 : 0, lo, hi);
+        for (int it = 0; it < max_iterations; ++it) {
+            if ((rc = dg_clf_kept_forward(h, bf.newimg, B, s, &logits))) return rc;
+            hipLaunchKernelGGL(cw_head_kernel, dim3((unsigned)N), dim3(256), 0, s, logits, n, P, batch_size, targeted ? 1 : 0, confidence, bf);
+            float* grad = nullptr;
+            if ((rc = dg_clf_seeded_backward(h, bf.seed, B, s, &grad))) return rc;
+            hipLaunchKernelGGL(cw_chunk_kernel, dim3((unsigned)chunks), dim3(256), 0, s, bf, B, batch_size, it,
+                               (abort_early && it % every == 0) ? 1 : 0);
+            const double t = it + 1;
+            const float lr_t = (float)((double)learning_rate * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.9, t)));
+            hipLaunchKernelGGL(cw_update_kernel, dim3(egrid), dim3(256), 0, s, bf, grad, x_adv, total, P, batch_size, it, lr_t, lo, hi);
+            CW_TRY(hipGetLastError());
+        }
+        if (chunk_stop)
+            CW_TRY(hipMemcpyAsync(chunk_stop + (long long)step * chunks, bf.abort_iter, chunks * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    }
+    if (final_const) {
+        if (binary_search_steps > 0)
+            hipLaunchKernelGGL(cw_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, P, batch_size, 1, 0, 0, targeted ? 1 : 0, lo, hi);
+        CW_TRY(hipGetLastError());
+        CW_TRY(hipMemcpyAsync(final_const, bf.cst, N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    if (best_l2) CW_TRY(hipMemcpyAsync(best_l2, bf.obestl2, N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (best_class) CW_TRY(hipMemcpyAsync(best_class, bf.obestscore, N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return DG_OK;
+}
+
+}  // extern "C"

@@ -362,6 +362,34 @@ def _mlp_input_gradient(self, x, labels=None, no_rec=False):
 MLP.input_gradient = _mlp_input_gradient
 
 
+def _mlp_backward(self, x, dlogits):
+    """d(sum_{b,k} dlogits[b,k] * logits(x)[b,k])/dx on the device (``dg_clf_backward``): the input gradient of any loss on
+    the logits, given its seed ``dlogits`` [B, nb_classes].  Bare classifier only (the reconstruction layer is not entered).
+    NumPy in gives NumPy out, torch in gives torch out on the caller's current stream."""
+    import torch
+    self._ensure()
+    if not self._weights_set:
+        raise _native.NativeError("classifier weights not set")
+    was_numpy = isinstance(x, np.ndarray)
+    dev = torch.device("cuda", self._device)
+    t = (torch.from_numpy(np.ascontiguousarray(x, np.float32)) if was_numpy else x).to(device=dev, dtype=torch.float32).contiguous()
+    d = (torch.from_numpy(np.ascontiguousarray(dlogits, np.float32)) if isinstance(dlogits, np.ndarray) else dlogits)
+    d = d.to(device=dev, dtype=torch.float32).contiguous()
+    if t.dim() != 4 or tuple(t.shape[1:]) != tuple(self.input_shape[1:]):
+        raise ValueError("x must be [B, %s], got %s" % (", ".join(str(v) for v in self.input_shape[1:]), tuple(t.shape)))
+    B = int(t.shape[0])
+    if tuple(d.shape) != (B, self.nb_classes):
+        raise ValueError("dlogits must be [%d, %d], got %s" % (B, self.nb_classes, tuple(d.shape)))
+    g = torch.empty_like(t)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _native.check(_native.load().dg_clf_backward(self._handle, t.data_ptr(), d.data_ptr(), B, g.data_ptr(), stream))
+    return g.cpu().numpy() if was_numpy else g
+
+
+MLP.backward = _mlp_backward
+
+
 class FastGradientMethod(object):
     """The cleverhans attack object the reference instantiates (whitebox.py:198-200, blackbox.py:530-534), ord = inf only:
     ``adv = clip(x + eps * sign(grad_x CE(model(x), y)), clip_min, clip_max)``; without ``y`` the model's own prediction is
@@ -402,6 +430,96 @@ class FastGradientMethod(object):
             _native.check(_native.load().dg_fgsm(m._handle, t.data_ptr(), lab.data_ptr() if lab is not None else None,
                                                  int(t.shape[0]), float(eps), lo, hi, out.data_ptr(), stream))
         return out.cpu().numpy() if was_numpy else out
+
+
+_CW_REC_NOTE = (
+    "CarliniWagnerL2 on a model with the Defense-GAN reconstruction layer attached (add_rec_model) is not implemented: in the "
+    "reference the gradient through ReconstructionLayer is identically zero (network_builder.py:266-271), so the attack "
+    "there reduces to repeated defended evaluations of the tanh round trip of x, whose per-iteration latent draws cannot be "
+    "pinned.  Build the attack before add_rec_model, or on a model without it (no_rec), as bench.py's --strong flow does for "
+    "FGSM.")
+
+
+class CarliniWagnerL2(object):
+    """cleverhans' CarliniWagnerL2 (the reference's ``--attack_type cw``, whitebox.py:201-209), restated and run as ONE
+    asynchronous device call (``dg_cw``; the algorithm is in defensegan_amd/csrc/dg_cw.hip's header comment and DESIGN.md
+    section 7).  ``sess`` / ``back`` are accepted for signature compatibility and ignored.
+
+    ``generate(x, y=None, y_target=None, **params)``: NumPy in gives NumPy out, a torch tensor in gives a tensor out (on the
+    caller's current stream, not waited for); ``y`` / ``y_target`` one-hot or class indices; without either the label is the
+    model's own first argmax on ``x``.  ``return_info=True`` also returns ``(best_l2, best_class)`` (1e10 / -1 where no step
+    succeeded); ``return_search=True`` then also ``(final_const [B] float64, chunk_stop [binary_search_steps, chunks] int32)``:
+    the constants after the last binary-search update and the iteration at whose check each chunk stopped (-1: it ran to
+    max_iterations).  ``nb_classes`` and ``feed`` are accepted and ignored.
+
+    ``abort_early`` changes which iterations count, not how long the call takes: a stopped chunk skips the attack's own
+    kernels, but the classifier's forward and backward keep running over every image until max_iterations.
+
+    The defaults are those of cleverhans 2.x ``generate`` as remembered (batch_size=1, confidence=0, learning_rate=5e-3,
+    binary_search_steps=5, max_iterations=1000, abort_early=True, initial_const=1e-2, clip_min=0, clip_max=1): nothing in the
+    reference pins them (cleverhans is an empty, un-pinned submodule).  Only the white-box setting is pinned:
+    ``binary_search_steps=1, max_iterations=100, learning_rate=10, initial_const=100, batch_size=BATCH_SIZE`` and no clip
+    bounds, so CelebA inputs are clipped to [0, 1] as well -- a quirk of the reference kept here.
+
+    A model with the reconstruction layer attached raises NotImplementedError (see _CW_REC_NOTE)."""
+
+    DEFAULTS = dict(batch_size=1, confidence=0.0, learning_rate=5e-3, binary_search_steps=5, max_iterations=1000, abort_early=True,
+                    initial_const=1e-2, clip_min=0.0, clip_max=1.0)
+
+    def __init__(self, model: MLP, back="tf", sess=None):
+        self.model = model
+
+    def generate(self, x, y=None, y_target=None, return_info=False, return_search=False, nb_classes=None, feed=None, **params):
+        import torch
+        unknown = set(params) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown CarliniWagnerL2 parameters: %s" % sorted(unknown))
+        p = dict(self.DEFAULTS, **params)
+        m = self.model
+        if m.rec_layer is not None:
+            raise NotImplementedError(_CW_REC_NOTE)
+        if y is not None and y_target is not None:
+            raise ValueError("give y or y_target, not both")
+        m._ensure()
+        if not m._weights_set:
+            raise _native.NativeError("classifier weights not set")
+        was_numpy = isinstance(x, np.ndarray)
+        dev = torch.device("cuda", m._device)
+        t = (torch.from_numpy(np.ascontiguousarray(x, np.float32)) if was_numpy else x).to(device=dev, dtype=torch.float32).contiguous()
+        if t.dim() != 4 or tuple(t.shape[1:]) != tuple(m.input_shape[1:]):
+            raise ValueError("x must be [B, %s], got %s" % (", ".join(str(d) for d in m.input_shape[1:]), tuple(t.shape)))
+        B = int(t.shape[0])
+        if B == 0:
+            raise ValueError("x holds no images")
+        lab, targeted = None, y_target is not None
+        yy = y_target if targeted else y
+        if yy is not None:
+            yy = np.asarray(yy if isinstance(yy, np.ndarray) else yy.detach().cpu().numpy())
+            if yy.ndim > 1:
+                yy = yy.argmax(axis=-1)                            # one-hot labels as cleverhans takes them
+            if yy.shape != (B,) or (yy < 0).any() or (yy >= m.nb_classes).any():
+                raise ValueError("labels must be %d class indices in [0, %d) or one-hot rows" % (B, m.nb_classes))
+            lab = torch.from_numpy(np.ascontiguousarray(yy)).to(device=dev, dtype=torch.int32)
+        out = torch.empty_like(t)
+        best_l2 = torch.empty(B, dtype=torch.float32, device=dev)
+        best_class = torch.empty(B, dtype=torch.int32, device=dev)
+        nsteps, chunks = max(int(p["binary_search_steps"]), 0), -(-B // max(int(p["batch_size"]), 1))
+        final_const = torch.empty(B, dtype=torch.float64, device=dev)
+        chunk_stop = torch.empty(nsteps, chunks, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _native.check(_native.load().dg_cw(
+                m._handle, t.data_ptr(), lab.data_ptr() if lab is not None else None, B, 1 if targeted else 0, int(p["batch_size"]),
+                float(p["confidence"]), float(p["learning_rate"]), int(p["binary_search_steps"]), int(p["max_iterations"]),
+                1 if p["abort_early"] else 0, float(p["initial_const"]), float(p["clip_min"]), float(p["clip_max"]), out.data_ptr(),
+                best_l2.data_ptr(), best_class.data_ptr(), final_const.data_ptr() if return_search else None,
+                chunk_stop.data_ptr() if return_search else None, stream))
+        res = (out, best_l2, best_class) + ((final_const, chunk_stop) if return_search else ())
+        if was_numpy:
+            res = tuple(r.cpu().numpy() for r in res)
+        if not return_info:
+            return res[0]
+        return res if return_search else res[:3]
 
 
 def rand_fgsm_prestep(test_images, eps: float, alpha: float, min_val: float = 0.0, max_val: float = 1.0, rng=None):

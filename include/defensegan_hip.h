@@ -290,6 +290,30 @@ int dg_eval_batch(dg_clf* h, const float* rec, const float* orig, const int32_t*
 int dg_clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float* grad, void* stream);
 int dg_fgsm(dg_clf* h, const float* x, const int32_t* labels, int B, float eps, float clip_min, float clip_max,
             float* x_adv, void* stream);
+/* grad [B,in_h,in_w,in_c] = d(sum_{b,k} dlogits[b,k] * logits(x)[b,k]) / dx for an arbitrary seed dlogits [B,n]: the backward
+ * chain of dg_clf_input_gradient (whose seed is dCE/dlogits) from any loss on the logits.  Device pointers; asynchronous. */
+int dg_clf_backward(dg_clf* h, const float* x, const float* dlogits, int B, float* grad, void* stream);
+
+/*
+ * The third white-box attack (/root/reference/whitebox.py:192-210, --attack_type cw; whitebox.py:201-209 sets
+ * binary_search_steps = 1, max_iterations = 100, learning_rate = 10, initial_const = 100, batch_size = BATCH_SIZE and no clip
+ * bounds, so [0, 1] also for CelebA): cleverhans' CarliniWagnerL2, restated (defensegan_amd/csrc/dg_cw.hip's header comment
+ * and DESIGN.md section 7 give the algorithm).  x [B,in_h,in_w,in_c]; labels [B] int32 = y, or y_target when `targeted`, or NULL
+ * for the model's own first argmax on x.  The B images run in chunks of batch_size (a trailing partial chunk is a chunk of its
+ * own) that share the abort-early decision and nothing else.  Out: x_adv [B,...] = the best successful newimg over all steps,
+ * clip(x) where none succeeded; best_l2 [B] (1e10 when none) and best_class [B] int32 (-1 when none); final_const [B] float64,
+ * the constants after the last step's binary-search update (initial_const is float64, as are the constants: cleverhans
+ * keeps them in NumPy float64); chunk_stop [binary_search_steps, ceil(B / batch_size)] int32, the
+ * iteration at whose check each chunk stopped in each outer step (-1: ran to max_iterations).  Every output but x_adv may be NULL.
+ * Device pointers; the whole attack is enqueued on `stream` with no host synchronisation and no graph capture.  A chunk that
+ * stopped early skips the attack's own kernels, but the classifier's forward and backward still run over all B images every
+ * iteration: abort_early changes the result, not the duration.  The workspace (about 6 x B x pixels floats) lives in the handle
+ * and grows on demand.
+ */
+int dg_cw(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted, int batch_size, float confidence,
+          float learning_rate, int binary_search_steps, int max_iterations, int abort_early, double initial_const,
+          float clip_min, float clip_max, float* x_adv, float* best_l2, int32_t* best_class, double* final_const,
+          int32_t* chunk_stop, void* stream);
 
 /*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
