@@ -54,6 +54,13 @@ SYMBOLS = [
     ("dg_fgsm", _i, [_vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
     ("dg_clf_backward", _i, [_vp, _vp, _vp, _i, _vp, _vp]),
     ("dg_cw", _i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _i, C.c_double, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dg_clf_set_dropout", _i, [_vp, _i, _f]),
+    ("dg_clf_get_weights", _i, [_vp, _i, _vp, _vp, _i]),
+    ("dg_clf_adam_reset", _i, [_vp]),
+    ("dg_clf_get_adam", _i, [_vp, _i, _vp, _vp, C.POINTER(_i64), _i]),
+    ("dg_clf_dropout_mask", _i, [_vp, _i, _i, _u64, _i64, _i, _vp, _vp]),
+    ("dg_clf_param_gradient", _i, [_vp, _vp, _vp, _i, _f, _f, _f, _u64, _i64, _vp, _vp, _vp, _vp]),
+    ("dg_clf_train", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _f, _u64, _vp, _vp]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/defensegan_hip.h"
+#include "dg_clf_internal.h"
 
 extern "C" __attribute__((visibility("hidden"))) void dg_set_error_message(const char* msg);   // dg_engine.cpp (dg_last_error storage), library-internal
 
@@ -35,6 +36,7 @@ struct ClfLayer {
     float* W = nullptr;
     float* b = nullptr;
     bool have_w = false;
+    float keep_prob = 0.f;       // Dropout: the reference's Dropout(prob), used by the training phase only (dg_clf_train.hip)
 };
 
 int fail(int code, const char* fmt, ...) {
@@ -260,6 +262,7 @@ struct dg_clf {
     size_t scores_floats = 0;
     int n_out = 0;
     CwWork* cw = nullptr;                     // Carlini-Wagner workspace (dg_cw.hip), grown on demand
+    TrainWork* tr = nullptr;                  // training workspace and Adam state (dg_clf_train.hip)
 };
 
 extern "C" {
@@ -293,6 +296,7 @@ int dg_clf_destroy(dg_clf* h) {
     for (float* p : h->gbuf)
         if (p) (void)hipFree(p);
     dg_cw_release(h->cw);
+    dg_train_release(h->tr);
     delete h;
     return DG_OK;
 }
@@ -383,6 +387,29 @@ int dg_clf_set_weights(dg_clf* h, int layer, const float* W, const int64_t* wsha
     CLF_TRY(hipMemcpy(l.W, W, n * sizeof(float), kind));
     CLF_TRY(hipMemcpy(l.b, b, (size_t)l.cout * sizeof(float), kind));
     l.have_w = true;
+    return DG_OK;
+}
+
+int dg_clf_set_dropout(dg_clf* h, int layer, float keep_prob) {
+    if (!h) return fail(DG_E_INVALID, "null handle");
+    if (layer < 0 || layer >= (int)h->layers.size() || h->layers[layer].kind != L_DROPOUT)
+        return fail(DG_E_INVALID, "layer %d is not a Dropout layer", layer);
+    if (!(keep_prob > 0.f && keep_prob <= 1.f)) return fail(DG_E_INVALID, "Dropout keep_prob %g outside (0, 1]", (double)keep_prob);
+    h->layers[layer].keep_prob = keep_prob;
+    return DG_OK;
+}
+
+int dg_clf_get_weights(dg_clf* h, int layer, float* W, float* b, int is_device) {
+    if (!h || !W || !b) return fail(DG_E_INVALID, "null argument");
+    if (layer < 0 || layer >= (int)h->layers.size()) return fail(DG_E_INVALID, "layer %d out of range", layer);
+    const ClfLayer& l = h->layers[layer];
+    if (l.kind != L_CONV && l.kind != L_LINEAR) return fail(DG_E_INVALID, "layer %d has no parameters", layer);
+    if (!l.have_w) return fail(DG_E_STATE, "layer %d has no weights", layer);
+    CLF_TRY(hipSetDevice(h->device));
+    const size_t nw = l.kind == L_CONV ? (size_t)l.kh * l.kw * l.cin * l.cout : (size_t)l.cin * l.cout;
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    CLF_TRY(hipMemcpy(W, l.W, nw * sizeof(float), kind));
+    CLF_TRY(hipMemcpy(b, l.b, (size_t)l.cout * sizeof(float), kind));
     return DG_OK;
 }
 
@@ -560,6 +587,60 @@ __attribute__((visibility("hidden"))) CwWork** dg_clf_cw_slot(dg_clf* h, int* de
     const int last = clf_last_layer(h);
     *n = last < 0 ? 0 : h->layers[last].oh * h->layers[last].ow * h->layers[last].oc;
     return &h->cw;
+}
+
+// ---- library-internal entries of the training path (dg_clf_train.hip, dg_clf_internal.h) ------------------------------
+__attribute__((visibility("hidden"))) int dg_clf_layer_count(const dg_clf* h) { return (int)h->layers.size(); }
+
+__attribute__((visibility("hidden"))) void dg_clf_layer_view(const dg_clf* h, int j, DgClfLayerView* v) {
+    const ClfLayer& l = h->layers[j];
+    *v = DgClfLayerView{l.kind, l.ih, l.iw, l.ic, l.oh, l.ow, l.oc, l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l,
+                        l.fused_relu ? 1 : 0, l.skip ? 1 : 0, l.keep_prob, l.W, l.b};
+}
+
+__attribute__((visibility("hidden"))) TrainWork** dg_clf_train_slot(dg_clf* h, int* device, int* P, int* have_weights) {
+    *device = h->device;
+    *P = h->in_h * h->in_w * h->in_c;
+    *have_weights = 1;
+    for (const auto& l : h->layers)
+        if ((l.kind == L_CONV || l.kind == L_LINEAR) && !l.have_w) *have_weights = 0;
+    return &h->tr;
+}
+
+__attribute__((visibility("hidden"))) void dg_clf_launch_forward(const dg_clf* h, int j, const float* in, float* out, int B, hipStream_t s) {
+    const ClfLayer& l = h->layers[j];
+    const long long total = (long long)B * l.oh * l.ow * l.oc;
+    const unsigned grid = (unsigned)((total + 255) / 256);
+    if (l.kind == L_CONV)
+        hipLaunchKernelGGL(clf_conv2d_kernel, dim3(grid), dim3(256), 0, s, in, l.W, l.b, out, total, l.ih, l.iw, l.ic, l.oh, l.ow,
+                           l.oc, l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
+    else if (l.kind == L_LINEAR)
+        hipLaunchKernelGGL(clf_linear_kernel, dim3(grid), dim3(256), 0, s, in, l.W, l.b, out, total, l.cin, l.cout, l.fused_relu ? 1 : 0);
+    else
+        hipLaunchKernelGGL(clf_relu_kernel, dim3(grid), dim3(256), 0, s, in, out, total);
+}
+
+__attribute__((visibility("hidden"))) void dg_clf_launch_input_grad(const dg_clf* h, int j, const float* g, const float* out, float* dx, int B,
+                                                                    hipStream_t s) {
+    const ClfLayer& l = h->layers[j];
+    const long long total = (long long)B * l.ih * l.iw * l.ic;
+    const unsigned grid = (unsigned)((total + 255) / 256);
+    if (l.kind == L_LINEAR)
+        hipLaunchKernelGGL(clf_linear_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, l.W, dx, total, l.cin, l.cout, l.fused_relu ? 1 : 0);
+    else if (l.kind == L_CONV)
+        hipLaunchKernelGGL(clf_conv2d_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, l.W, dx, total, l.ih, l.iw, l.ic, l.oh, l.ow, l.oc,
+                           l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
+    else
+        hipLaunchKernelGGL(clf_relu_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, dx, total);
+}
+
+__attribute__((visibility("hidden"))) void dg_clf_launch_ce_grad(const float* logits, const int32_t* labels, float* g, int B, int n, hipStream_t s) {
+    hipLaunchKernelGGL(clf_ce_grad_kernel, dim3((B + 63) / 64), dim3(64), 0, s, logits, labels, g, B, n);
+}
+
+__attribute__((visibility("hidden"))) void dg_clf_launch_fgsm(const float* x, const float* grad, float* xadv, long long total, float eps, float lo,
+                                                              float hi, hipStream_t s) {
+    hipLaunchKernelGGL(clf_fgsm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, grad, xadv, total, eps, lo, hi);
 }
 
 int dg_clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float* grad, void* stream) {

@@ -6,9 +6,11 @@ the arithmetic runs in the HIP library (dg_clf_* in include/defensegan_hip.h), n
     model.set_weights([(kernels, b), ...]) # one (W, b) per Conv2D / Linear layer, reference layouts
     probs = model(x)                       # = get_probs(x); x NumPy or torch [B,H,W,C]; returns the same kind
     model.add_rec_model(gan, z_init, batch_size)   # prepend the Defense-GAN projection (network_builder.py:179-183)
+    model.save_weights("clf.npz"); model.load_weights("clf.npz")   # trained parameters (utils_tf.model_train)
 
 Differences from the reference that follow from having no TF graph: ``fprop`` exposes only 'logits' and 'probs' (and
-'reconstruction' after add_rec_model), not every hidden layer; Dropout is the identity (evaluation phase)."""
+'reconstruction' after add_rec_model), not every hidden layer; Dropout is the identity in evaluation and active only in
+training (utils_tf.model_train)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -65,7 +67,8 @@ class Softmax(Layer):
 
 
 class Dropout(Layer):
-    """Identity at evaluation (tf.cond(K.learning_phase(), ...), network_builder.py:296-297)."""
+    """Identity at evaluation (tf.cond(K.learning_phase(), ...), network_builder.py:296-297).  In training, ``prob`` is TF 1.x
+    tf.nn.dropout's KEEP probability, as the reference passes it: Dropout(0.25) keeps 25 % of the units and scales them by 4."""
 
     def __init__(self, prob):
         self.prob = prob
@@ -106,6 +109,8 @@ class MLP(object):
             if rc < 0:
                 _native.check(rc)
             self._native_index.append(rc)
+            if isinstance(layer, Dropout):
+                _native.check(lib.dg_clf_set_dropout(h, rc, float(layer.prob)))
         self.nb_classes = int(lib.dg_clf_output_width(h))
 
     def close(self):
@@ -135,6 +140,57 @@ class MLP(object):
             _native.check(lib.dg_clf_set_weights(self._handle, self._native_index[li], W.ctypes.data_as(C.c_void_p), shp, W.ndim,
                                                  b.ctypes.data_as(C.c_void_p), b.size, 0))
         self._weights_set = True
+
+    def param_shapes(self) -> List[Tuple[Tuple[int, ...], Tuple[int]]]:
+        """((W shape), (b shape)) per Conv2D / Linear layer, in order, in the reference layouts."""
+        _, H, W, Cc = self.input_shape
+        shape, flat, out = (H, W, Cc), None, []
+        for layer in self.layers:
+            if isinstance(layer, Conv2D):
+                out.append((tuple(layer.kernel_shape) + (shape[2], layer.output_channels), (layer.output_channels,)))
+                shape = conv_output_shape(shape, layer)
+            elif isinstance(layer, Flatten):
+                flat = int(np.prod(shape))
+            elif isinstance(layer, Linear):
+                out.append(((flat, layer.num_hid), (layer.num_hid,)))
+                flat = layer.num_hid
+        return out
+
+    def get_weights(self) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """The device parameters as NumPy (W, b) pairs, one per Conv2D / Linear layer, in the layouts set_weights takes."""
+        self._ensure()
+        if not self._weights_set:
+            raise _native.NativeError("classifier weights not set")
+        lib = _native.load()
+        out = []
+        for li, (ws, bs) in zip(self._param_layers, self.param_shapes()):
+            W, b = np.empty(ws, np.float32), np.empty(bs, np.float32)
+            _native.check(lib.dg_clf_get_weights(self._handle, self._native_index[li], W.ctypes.data_as(C.c_void_p),
+                                                 b.ctypes.data_as(C.c_void_p), 0))
+            out.append((W, b))
+        return out
+
+    def save_weights(self, path: str) -> None:
+        """Writes get_weights() to ``path`` (.npz: W0, b0, W1, b1, ... in layer order)."""
+        arrays = {}
+        for i, (W, b) in enumerate(self.get_weights()):
+            arrays["W%d" % i], arrays["b%d" % i] = W, b
+        with open(path, "wb") as fh:
+            np.savez(fh, **arrays)
+
+    def load_weights(self, path: str) -> None:
+        """Installs the parameters save_weights wrote; the file must hold exactly this model's (W, b) pairs and shapes."""
+        shapes = self.param_shapes()
+        with np.load(path) as f:
+            keys = set(f.files)
+            want = {"%s%d" % (k, i) for i in range(len(shapes)) for k in "Wb"}
+            if keys != want:
+                raise ValueError("%s holds %s, this model needs %s" % (path, sorted(keys), sorted(want)))
+            params = [(f["W%d" % i], f["b%d" % i]) for i in range(len(shapes))]
+        for i, ((W, b), (ws, bs)) in enumerate(zip(params, shapes)):
+            if W.shape != ws or b.shape != bs:
+                raise ValueError("%s: parameter pair %d is %s / %s, this model needs %s / %s" % (path, i, W.shape, b.shape, ws, bs))
+        self.set_weights(params)
 
     def init_like_reference(self, seed: int = 0) -> List[Tuple[np.ndarray, np.ndarray]]:
         """The reference's initialisers (normal, normalised per output unit, zero bias: network_builder.py:196-203, 217-224)

@@ -258,7 +258,8 @@ typedef struct dg_clf dg_clf;
 #define DG_LAYER_LINEAR 2     /* p0 = num_hid                                                                    */
 #define DG_LAYER_FLATTEN 3
 #define DG_LAYER_SOFTMAX 4
-#define DG_LAYER_DROPOUT 5    /* identity: K.learning_phase() is 0 at evaluation (network_builder.py:296-297)     */
+#define DG_LAYER_DROPOUT 5    /* identity: K.learning_phase() is 0 at evaluation (network_builder.py:296-297);    *
+                               * active in training (dg_clf_set_dropout)                                          */
 
 /* An empty MLP for NHWC inputs [*, in_h, in_w, in_c] (network_builder.py:129-162). */
 int dg_clf_create(int device, int in_h, int in_w, int in_c, dg_clf** out);
@@ -314,6 +315,42 @@ int dg_cw(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted,
           float learning_rate, int binary_search_steps, int max_iterations, int abort_early, double initial_const,
           float clip_min, float clip_max, float* x_adv, float* best_l2, int32_t* best_class, double* final_const,
           int32_t* chunk_stop, void* stream);
+
+/*
+ * Classifier training (the reference's whitebox.py:120-170 and blackbox.py's prep_bbox: cleverhans utils_tf.model_train with Adam,
+ * `--defense_type adv_tr` adding FGSM inputs of the current model, whitebox.py:147-163; cleverhans is an empty, un-pinned submodule,
+ * its published model_train / model_loss is restated in defensegan_amd/csrc/dg_clf_train.hip's header comment and DESIGN.md
+ * section 7).  Replaces the TF graph of model_train: the training-phase forward (K.learning_phase() = 1, Dropout active), the
+ * softmax cross-entropy on the logits, tf.gradients over every Conv2D / Linear parameter and AdamOptimizer.minimize.  The
+ * evaluation forward stays dg_clf_forward.  All pointers are device pointers unless `is_device` says otherwise; every call is
+ * asynchronous on `stream` and the workspace grows on demand in the handle.
+ */
+/* The training phase of a Dropout layer: the reference's Dropout(prob) hands `prob` to TF 1.x tf.nn.dropout as KEEP_prob
+ * (network_builder.py:296-297), so Dropout(0.25) keeps 25 % of the units, scaled by 4.  Required before training a model that
+ * has Dropout layers. */
+int dg_clf_set_dropout(dg_clf* h, int layer, float keep_prob);
+/* Reads a Conv2D / Linear layer's parameters back, in the layouts of dg_clf_set_weights (what a TF saver would hold). */
+int dg_clf_get_weights(dg_clf* h, int layer, float* W, float* b, int is_device);
+/* A fresh AdamOptimizer (what each model_train call builds): m = v = 0, t = 0.  Synchronous. */
+int dg_clf_adam_reset(dg_clf* h);
+/* A layer's Adam state: m and v [(W; b) flattened, W first] and the step count t (host).  Any of m, v, t may be NULL. */
+int dg_clf_get_adam(dg_clf* h, int layer, float* m, float* v, int64_t* t, int is_device);
+/* The mask [B, features] a Dropout layer draws in the forward `pass` (0 clean, 1 the adversarial half's inner FGSM forward,
+ * 2 the forward on x_adv) of step `step` under `seed`: floor(keep + u), u from Philox4x32-10 (dg_clf_train.hip). */
+int dg_clf_dropout_mask(dg_clf* h, int layer, int B, uint64_t seed, int64_t step, int pass, float* mask, void* stream);
+/* The gradient of one training step on x [B,...], labels [B] int32, with no parameter change: grads = every Conv2D / Linear
+ * layer's (dW, db) in layer order, each flattened in the reference layout, W before b; *loss = the step's mean cross-entropy (with
+ * adv_eps > 0: (clean + adversarial) / 2); x_adv [B,...] (may be NULL) = the adversarial inputs, clip(x + adv_eps * sign(...),
+ * clip_min, clip_max).  adv_eps <= 0: no adversarial half.  Dropout masks are drawn with (seed, step). */
+int dg_clf_param_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float adv_eps, float clip_min, float clip_max,
+                          uint64_t seed, int64_t step, float* grads, float* loss, float* x_adv, void* stream);
+/* n_steps Adam steps of model_train: step s trains on the images X[idx[s*batch_size + i]], i < batch_size, of the n images
+ * X [n,...] with labels [n] int32 (the batch schedule is the caller's; an index outside [0, n) reads a zero image that
+ * contributes nothing); losses [n_steps] (may be NULL) = each step's loss.  The Adam step count t continues from the last
+ * call (dg_clf_adam_reset restarts it); step s draws its Dropout masks with (seed, t before the step).  A whole epoch is
+ * enqueued with no host synchronisation and no graph capture. */
+int dg_clf_train(dg_clf* h, const float* X, const int32_t* labels, int n, const int32_t* idx, int n_steps, int batch_size,
+                 float learning_rate, float adv_eps, float clip_min, float clip_max, uint64_t seed, float* losses, void* stream);
 
 /*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
