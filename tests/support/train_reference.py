@@ -98,9 +98,10 @@ def step_masks(layers, input_shape, B, seed, step, pass_):
 
 
 # ---------------------------------------------------------------------- training-phase forward, loss, gradients
-def logits(layers, params, x, masks=None):
+def logits(layers, params, x, masks=None, pre=None):
     """x [B,H,W,C] float64 tensor (NHWC) -> logits (the Softmax layer's input).  ``params``: list of (W, b) float64 tensors.
-    ``masks``: {layer: [B, features] array} for the training phase (Dropout y = (x / keep) * mask); None: evaluation."""
+    ``masks``: {layer: [B, features] array} for the training phase (Dropout y = (x / keep) * mask); None: evaluation.
+    ``pre``: a list that receives every ReLU layer's input."""
     h = x
     it = iter(params)
     for j, L in enumerate(layers):
@@ -118,6 +119,8 @@ def logits(layers, params, x, masks=None):
             W, b = next(it)
             h = h @ W + b
         elif kind == "relu":
+            if pre is not None:
+                pre.append(h)
             h = torch.relu(h)
         elif kind == "flatten":
             h = h.reshape(h.shape[0], -1)
@@ -131,7 +134,13 @@ def logits(layers, params, x, masks=None):
 
 
 def mean_ce(z, labels):
-    return F.cross_entropy(z, torch.as_tensor(np.asarray(labels), dtype=torch.long))
+    """Mean cross-entropy over the batch.  A negative label marks an image without a label (what dg_clf_train's gather makes of an
+    index outside the set): it adds nothing to the sum, and the divisor stays the batch size."""
+    y = torch.as_tensor(np.asarray(labels), dtype=torch.long)
+    if bool((y < 0).any()):
+        y = torch.where(y < 0, torch.full_like(y, -1), y)
+        return F.cross_entropy(z, y, ignore_index=-1, reduction="sum") / z.shape[0]
+    return F.cross_entropy(z, y)
 
 
 def as_params(params, requires_grad=False):
@@ -166,6 +175,21 @@ def param_gradient(layers, params, x, labels, seed, step, adv_eps=0.0, lo=0.0, h
     g = torch.autograd.grad(loss, flat)
     grads = [(g[2 * i].numpy(), g[2 * i + 1].numpy()) for i in range(len(p))]
     return float(loss.item()), grads, (None if xa is None else xa.numpy())
+
+
+def relu_margins(layers, params, x, masks=None):
+    """Per image: the smallest non-zero |ReLU input| of the float64 forward.  The gradient jumps where a ReLU input crosses zero:
+    an input closer to zero than float32 rounding of the sum that forms it (about 1e-7 for the unit-norm weight columns of the
+    zoo) is decided one way in float64 and the other way in float32, and a float32 gradient then differs from the float64 one by
+    that activation's whole term.  A comparison of the two is meaningful only at inputs whose margin is well above that; exact
+    zeros (a zero image under zero biases) are "not > 0" on both sides and do not count."""
+    pre = []
+    logits(layers, as_params(params), torch.as_tensor(np.asarray(x, np.float64)), masks, pre=pre)
+    out = np.full(len(x), np.inf)
+    for h in pre:
+        a = np.abs(h.numpy()).reshape(len(x), -1)
+        out = np.minimum(out, np.where(a > 0, a, np.inf).min(axis=1))
+    return out
 
 
 def loss_of(layers, params, x, labels, masks):
@@ -205,3 +229,93 @@ def train(layers, params, X, labels, idx, batch_size, lr, seed, adv_eps=0.0, lo=
             nxt.append((W, b))
         params = nxt
     return np.asarray(losses), params
+
+
+# ---------------------------------------------------------------------- the weight-gradient planner, restated
+# dg_clf_train.hip's geometry() and slot_plan(): a layer's weight gradient is a GEMM [M + 1, K] x [K, N] (row M: the bias) in
+# 64 x 64 output tiles; the reduction axis K = B * output positions is cut into `slots` runs of Kc terms, each walked in chunks
+# of 16.  Restated so that the tests can say which regime of the kernel each of their cases reaches, and pick the images that
+# sit on a slot boundary.
+WT, WKC = 64, 16
+
+
+def wgrad_shapes(layers, input_shape):
+    """Per Conv2D / Linear layer: (kind, M, N, positions): M = kh * kw * cin (Linear: its inputs), N = its outputs, positions =
+    oh * ow output positions per image (Linear: 1)."""
+    H, W, Cc = input_shape
+    out, flat = [], None
+    for L in layers:
+        if L[0] == "conv":
+            (kh, kw), (sh, sw) = L[2], L[3]
+            M = kh * kw * Cc
+            if L[4] == "SAME":
+                H, W = -(-H // sh), -(-W // sw)
+            else:
+                H, W = (H - kh) // sh + 1, (W - kw) // sw + 1
+            Cc = L[1]
+            out.append(("conv", M, Cc, H * W))
+        elif L[0] == "flatten":
+            flat = H * W * Cc
+        elif L[0] == "linear":
+            out.append(("linear", flat, L[1], 1))
+            flat = L[1]
+    return out
+
+
+def slot_plan(M, N, K):
+    """(tiles, S, Kc, slots): about 1024 workgroups per layer, at least 64 terms per slot, at most 256 slots."""
+    tiles = -(-(M + 1) // WT) * -(-N // WT)
+    S = max(1, 1024 // tiles)
+    S = min(S, max(1, K // 64), 256)
+    Kc = -(-K // S)
+    return tiles, S, Kc, -(-K // Kc)
+
+
+REGIMES = ("linear layer with >= 2 slots of >= 2 chunks", "256-slot cap", "slot start off a chunk boundary", "slots < S", "K < 16",
+           "K a multiple of 16", "ragged last M-tile", "ragged last N-tile", "N < 4")
+
+
+def regimes(kind, M, N, positions, B):
+    """The regimes of REGIMES that one layer's weight gradient reaches at batch size B."""
+    K = B * positions
+    _, S, Kc, slots = slot_plan(M, N, K)
+    hit = {"linear layer with >= 2 slots of >= 2 chunks": kind == "linear" and slots >= 2 and Kc > WKC,
+           "256-slot cap": S == 256,
+           "slot start off a chunk boundary": slots >= 2 and Kc % WKC != 0,
+           "slots < S": slots < S,
+           "K < 16": K < WKC,
+           "K a multiple of 16": K % WKC == 0,
+           "ragged last M-tile": M + 1 > WT and (M + 1) % WT != 0,
+           "ragged last N-tile": N > WT and N % WT != 0,
+           "N < 4": N < 4}
+    return {r for r in REGIMES if hit[r]}
+
+
+def boundary_images(layers, input_shape, B):
+    """The images whose terms lie next to a slot boundary in some layer: image 0 and B - 1 (the first and last k), and for each
+    layer's first and last boundary kb = z * Kc the image holding term kb - 1 and the one holding kb (the same image when the
+    boundary cuts inside it, as Kc = 98 cuts the 196 positions of a 14 x 14 output)."""
+    out = {0, B - 1}
+    for kind, M, N, pos in wgrad_shapes(layers, input_shape):
+        _, _, Kc, slots = slot_plan(M, N, B * pos)
+        for z in {1, slots - 1} - {0}:
+            out |= {(z * Kc - 1) // pos, (z * Kc) // pos}
+    return sorted(out)
+
+
+# ---------------------------------------------------------------------- the cases of tests/test_gpu_train_shapes.py
+def shape_model(key):
+    """A letter of network_builder.MODELS at its full width, or "A16c": model A with 16 filters and 2 classes on 64 x 64 x 3."""
+    from defensegan_amd import network_builder as nb
+    if key == "A16c":
+        return nb.model_a(nb_filters=16, nb_classes=2, input_shape=(None, 64, 64, 3))
+    return nb.MODELS[key]()
+
+
+# (model, batch size, adv_eps) of the weight-gradient value checks: E (Linear only) and F (convolutions) over the batch sizes,
+# D, Y, Q, Z at a small and at the shipped batch size, the colour model.  tests/test_train_cpu.py asserts that every regime of
+# REGIMES is reached by a layer of one of them.
+BATCH_SIZES = (1, 16, 17, 64, 100, 128, 130, 200)
+GRADIENT_CASES = ([(name, B, 0.0) for name in "EF" for B in BATCH_SIZES] + [("E", 128, 0.15), ("F", 128, 0.15)] +
+                  [("D", 5, 0.0), ("D", 128, 0.0), ("Y", 3, 0.0), ("Y", 128, 0.0), ("Q", 3, 0.0), ("Q", 128, 0.0), ("Z", 3, 0.0),
+                   ("Z", 128, 0.0), ("A16c", 37, 0.15)])

@@ -218,3 +218,79 @@ def test_weight_file_round_trips(tmp_path, monkeypatch):
     np.savez(path, **wrong)
     with pytest.raises(ValueError, match="parameter pair 1"):
         m.load_weights(path)
+
+
+# ---------------------------------------------------------------------- the cases of tests/test_gpu_train_shapes.py
+def test_slot_plan_restatement_worked_by_hand():
+    """dg_clf_train.hip's slot_plan on cases worked by hand: (tiles, S, Kc, slots)."""
+    assert R.slot_plan(784, 200, 128) == (52, 2, 64, 2)            # model E first Linear, B = 128
+    assert R.slot_plan(784, 200, 100) == (52, 1, 100, 1)           # one slot, the last chunk holds 4 terms
+    assert R.slot_plan(784, 200, 130) == (52, 2, 65, 2)            # slot 1 starts at k = 65
+    assert R.slot_plan(64, 64, 128 * 196) == (2, 256, 98, 256)     # model F first convolution at the cap, Kc cuts an image in two
+    assert R.slot_plan(64, 64, 200 * 196) == (2, 256, 154, 255)    # ceil(K / Kc) < S
+    assert R.slot_plan(9 * 128, 128, 128) == (19 * 2, 2, 64, 2)    # model Z's last convolution: 19 M-tiles
+    m = nb.model_f()
+    assert R.wgrad_shapes(R.describe(m), (28, 28, 1)) == [("conv", 64, 64, 196), ("conv", 2304, 128, 25), ("conv", 3200, 128, 1),
+                                                          ("linear", 128, 10, 1)]
+    assert R.boundary_images(R.describe(nb.model_e()), (28, 28, 1), 130) == [0, 64, 65, 129]
+    # F at 128: Kc = 98 cuts images 0 and 127 of the first convolution, Kc = 247 cuts images 9 (k 225 .. 249) and 118 of the second
+    assert R.boundary_images(R.describe(m), (28, 28, 1), 128) == [0, 9, 63, 64, 118, 127]
+
+
+def test_gradient_cases_reach_every_regime_of_the_weight_gradient_kernel():
+    """Each regime of tr_wgrad_kernel / slot_plan is reached by a layer of a case that tests/test_gpu_train_shapes.py compares
+    with float64.  A planner change that moves the regimes shows here as the regime that lost its case."""
+    reached = {r: [] for r in R.REGIMES}
+    for key, B, _ in R.GRADIENT_CASES:
+        m = R.shape_model(key)
+        for i, (kind, M, N, pos) in enumerate(R.wgrad_shapes(R.describe(m), m.input_shape[1:])):
+            for r in R.regimes(kind, M, N, pos, B):
+                reached[r].append((key, B, i))
+    missing = [r for r in R.REGIMES if not reached[r]]
+    assert not missing, "no gradient case reaches: %s" % "; ".join(missing)
+    # the cases the regimes were chosen by
+    assert ("E", 128, 0) in reached["linear layer with >= 2 slots of >= 2 chunks"]
+    assert ("F", 128, 0) in reached["256-slot cap"] and ("F", 128, 0) in reached["slot start off a chunk boundary"]
+    assert ("E", 130, 0) in reached["slot start off a chunk boundary"]
+    assert ("F", 200, 0) in reached["slots < S"]
+    assert ("E", 1, 0) in reached["K < 16"] and ("E", 16, 0) in reached["K a multiple of 16"]
+    assert ("Z", 128, 5) in reached["ragged last M-tile"] and ("Z", 128, 7) in reached["ragged last N-tile"]
+    assert ("A16c", 37, 3) in reached["N < 4"]
+    # every model of the zoo is differentiated at a batch size of at least 128 or by the older small-batch tests
+    assert {k for k, _, _ in R.GRADIENT_CASES} >= set("DEFYQZ") and set(nb.MODELS) == set("ABCDEFYQZ")
+
+
+def test_reference_gives_zero_weight_gradients_for_zero_images_with_zero_biases():
+    """What the isolated-image GPU tests rest on: with zero biases and ReLU, an all-zero image has zero activations in every layer
+    and a zero masked gradient in every ReLU layer, so it adds exactly nothing to any dW (db of the logits layer still sums over
+    all images).  Checked on the float64 reference alone, for a Linear-only and a convolutional model."""
+    for name in ("E", "F"):
+        m = nb.MODELS[name]()
+        layers = R.describe(m)
+        rs = np.random.RandomState(1)
+        params = [(rs.standard_normal(ws) * 0.1, np.zeros(bs)) for ws, bs in m.param_shapes()]
+        y = rs.randint(0, 10, 4)
+        x = np.zeros((4, 28, 28, 1))
+        _, grads, _ = R.param_gradient(layers, params, x, y, seed=1, step=0)
+        for dW, _ in grads:
+            assert not dW.any()
+        assert grads[-1][1].any() and not any(db.any() for _, db in grads[:-1])
+        # one non-zero image among zeros: its gradient is that image's own term of the sum, whatever the zero images' labels are
+        x[2] = rs.uniform(0, 1, (28, 28, 1))
+        _, g1, _ = R.param_gradient(layers, params, x, y, seed=1, step=0)
+        y2 = y.copy()
+        y2[[0, 1, 3]] = (y2[[0, 1, 3]] + 1) % 10
+        _, g2, _ = R.param_gradient(layers, params, x, y2, seed=1, step=0)
+        for (dW, _), (dW2, _) in zip(g1, g2):
+            assert dW.any()
+            np.testing.assert_array_equal(dW, dW2)
+
+
+def test_reference_loss_ignores_an_image_without_a_label_and_keeps_the_divisor():
+    import torch
+    z = torch.tensor([[1.0, 2.0, 0.5], [0.3, -1.0, 2.0], [0.0, 0.0, 0.0]], dtype=torch.float64)
+    full = float(R.mean_ce(z, [2, 0, 1]))
+    part = float(R.mean_ce(z, [2, -1, 1]))
+    ce = -torch.log_softmax(z, dim=1).numpy()
+    assert abs(full - (ce[0, 2] + ce[1, 0] + ce[2, 1]) / 3) < 1e-15
+    assert abs(part - (ce[0, 2] + ce[2, 1]) / 3) < 1e-15
