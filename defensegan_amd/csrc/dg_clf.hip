@@ -13,33 +13,11 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
-#include <string>
 #include <vector>
 
-#include "../../include/defensegan_hip.h"
 #include "dg_clf_internal.h"
 
-extern "C" __attribute__((visibility("hidden"))) void dg_set_error_message(const char* msg);   // dg_engine.cpp (dg_last_error storage), library-internal
-
-namespace {
-
-enum LayerKind { L_CONV = 0, L_RELU = 1, L_LINEAR = 2, L_FLATTEN = 3, L_SOFTMAX = 4, L_DROPOUT = 5 };
-
-struct ClfLayer {
-    int kind = 0;
-    // conv
-    int kh = 0, kw = 0, sh = 1, sw = 1, same = 0, cin = 0, cout = 0, pad_t = 0, pad_l = 0;
-    // shapes (per image)
-    int ih = 0, iw = 0, ic = 0, oh = 0, ow = 0, oc = 0;
-    bool fused_relu = false;     // the ReLU that follows is applied in this layer's kernel
-    bool skip = false;           // a ReLU folded into its predecessor / identity layers
-    float* W = nullptr;
-    float* b = nullptr;
-    bool have_w = false;
-    float keep_prob = 0.f;       // Dropout: the reference's Dropout(prob), used by the training phase only (dg_clf_train.hip)
-};
-
-int fail(int code, const char* fmt, ...) {
+int clf_fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -49,11 +27,7 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define CLF_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return fail(DG_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
+namespace {
 
 // y[b, oh, ow, co] = bias[co] + sum_{kh,kw,ci} x[b, oh*sh + kh - pad_t, ow*sw + kw - pad_l, ci] * K[kh, kw, ci, co]
 // (cross-correlation, tf.nn.conv2d; out-of-range taps are the zero padding).  One thread per output, co fastest.
@@ -242,36 +216,130 @@ __global__ __launch_bounds__(256) void clf_fgsm_kernel(const float* __restrict__
 
 }  // namespace
 
-struct CwWork;
-extern "C" __attribute__((visibility("hidden"))) void dg_cw_release(CwWork* w);     // dg_cw.hip
+// ---- library-internal entries (dg_clf_internal.h): the one place each kernel is launched from ------------------------------------
+int clf_missing_weights(const dg_clf* h) {
+    for (size_t j = 0; j < h->layers.size(); ++j)
+        if (h->layers[j].has_params() && !h->layers[j].have_w) return (int)j;
+    return -1;
+}
 
-struct dg_clf {
-    int device = 0;
-    int in_h = 0, in_w = 0, in_c = 0;
-    std::vector<ClfLayer> layers;
-    bool planned = false;
-    int cur_h = 0, cur_w = 0, cur_c = 0;      // running shape while layers are added (flat: h = w = 1, c = width)
-    bool flat = false;
-    float* buf[2] = {nullptr, nullptr};
-    size_t buf_floats = 0;
-    float* scores = nullptr;                  // [B, n_out] scratch of dg_eval_batch
-    std::vector<float*> acts;                 // per-layer outputs kept by the gradient path
-    std::vector<size_t> acts_floats;
-    float* gbuf[2] = {nullptr, nullptr};      // gradient ping-pong
-    size_t gbuf_floats = 0;
-    size_t scores_floats = 0;
-    int n_out = 0;
-    CwWork* cw = nullptr;                     // Carlini-Wagner workspace (dg_cw.hip), grown on demand
-    TrainWork* tr = nullptr;                  // training workspace and Adam state (dg_clf_train.hip)
-};
+void clf_launch_forward(const dg_clf* h, int j, const float* in, float* out, int B, hipStream_t s) {
+    const ClfLayer& l = h->layers[j];
+    const long long total = (long long)B * l.features();
+    const unsigned grid = (unsigned)((total + 255) / 256);
+    if (l.kind == DG_LAYER_CONV2D)
+        hipLaunchKernelGGL(clf_conv2d_kernel, dim3(grid), dim3(256), 0, s, in, l.W, l.b, out, total, l.ih, l.iw, l.ic, l.oh, l.ow,
+                           l.oc, l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
+    else if (l.kind == DG_LAYER_LINEAR)
+        hipLaunchKernelGGL(clf_linear_kernel, dim3(grid), dim3(256), 0, s, in, l.W, l.b, out, total, l.cin, l.cout, l.fused_relu ? 1 : 0);
+    else
+        hipLaunchKernelGGL(clf_relu_kernel, dim3(grid), dim3(256), 0, s, in, out, total);
+}
+
+void clf_launch_input_grad(const dg_clf* h, int j, const float* g, const float* out, float* dx, int B, hipStream_t s) {
+    const ClfLayer& l = h->layers[j];
+    const long long total = (long long)B * l.ih * l.iw * l.ic;
+    const unsigned grid = (unsigned)((total + 255) / 256);
+    if (l.kind == DG_LAYER_LINEAR)
+        hipLaunchKernelGGL(clf_linear_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, l.W, dx, total, l.cin, l.cout, l.fused_relu ? 1 : 0);
+    else if (l.kind == DG_LAYER_CONV2D)
+        hipLaunchKernelGGL(clf_conv2d_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, l.W, dx, total, l.ih, l.iw, l.ic, l.oh, l.ow, l.oc,
+                           l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
+    else
+        hipLaunchKernelGGL(clf_relu_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, dx, total);
+}
+
+void clf_launch_ce_grad(const float* logits, const int32_t* labels, float* g, int B, int n, hipStream_t s) {
+    hipLaunchKernelGGL(clf_ce_grad_kernel, dim3((B + 63) / 64), dim3(64), 0, s, logits, labels, g, B, n);
+}
+
+void clf_launch_fgsm(const float* x, const float* grad, float* xadv, long long total, float eps, float lo, float hi, hipStream_t s) {
+    hipLaunchKernelGGL(clf_fgsm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, grad, xadv, total, eps, lo, hi);
+}
+
+// The forward walk.  keep: every layer's output stays in h->acts (the gradient path needs them afterwards), otherwise the
+// layers ping-pong through h->buf and the logits go to `logits` when given.
+static int clf_run(dg_clf* h, const float* x, int B, float* logits, float* probs, hipStream_t s, bool keep = false) {
+    const int missing = clf_missing_weights(h);
+    if (missing >= 0) return clf_fail(DG_E_STATE, "classifier layer %d has no weights", missing);
+    size_t need = 0;
+    for (const auto& l : h->layers) need = std::max(need, (size_t)(B * l.features()));
+    int rc = clf_grow(h->buf, 2, h->buf_floats, need);
+    if (rc) return rc;
+    if (h->logit_layer < 0) return clf_fail(DG_E_STATE, "classifier has no layers");
+    if (keep && h->acts.size() < h->layers.size()) { h->acts.resize(h->layers.size(), nullptr); h->acts_floats.resize(h->layers.size(), 0); }
+    const float* cur = x;
+    int which = 0;
+    for (int j = 0; j < (int)h->layers.size(); ++j) {
+        const ClfLayer& l = h->layers[j];
+        if (l.skip || l.kind == DG_LAYER_SOFTMAX) continue;
+        float* out = (j == h->logit_layer && logits) ? logits : h->buf[which];
+        if (keep) {
+            if ((rc = clf_grow(&h->acts[j], 1, h->acts_floats[j], (size_t)B * l.features()))) return rc;
+            out = h->acts[j];
+        }
+        clf_launch_forward(h, j, cur, out, B, s);
+        cur = out;
+        which ^= 1;
+    }
+    if (probs) {
+        if (h->has_softmax)
+            hipLaunchKernelGGL(clf_softmax_kernel, dim3((B + 63) / 64), dim3(64), 0, s, cur, probs, B, h->n_logits);
+        else
+            CLF_TRY(hipMemcpyAsync(probs, cur, (size_t)B * h->n_logits * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    CLF_TRY(hipGetLastError());
+    return DG_OK;
+}
+
+int clf_kept_forward(dg_clf* h, const float* x, int B, hipStream_t s) { return clf_run(h, x, B, nullptr, nullptr, s, /*keep=*/true); }
+
+static int clf_grow_gbuf(dg_clf* h, int B) {
+    size_t need = (size_t)B * h->pixels();
+    for (const auto& l : h->layers) need = std::max(need, (size_t)(B * l.features()));
+    return clf_grow(h->gbuf, 2, h->gbuf_floats, need);
+}
+
+// The seed-agnostic chain: g = seed [B, n] = dLoss/dlogits -> dLoss/dx, through the layer outputs the last clf_kept_forward left
+// in h->acts.  The result lies in one of the gbuf ping-pong buffers (never in `seed`).
+static int clf_backward_chain(dg_clf* h, const float* seed, int B, float** grad, hipStream_t s) {
+    int which = 0;
+    const float* g = seed;
+    for (int j = h->logit_layer; j >= 0; --j) {
+        const ClfLayer& l = h->layers[j];
+        if (l.skip || l.kind == DG_LAYER_SOFTMAX) continue;
+        float* dx = h->gbuf[which ^ 1];
+        clf_launch_input_grad(h, j, g, h->acts[j], dx, B, s);
+        which ^= 1;
+        g = dx;
+    }
+    CLF_TRY(hipGetLastError());
+    *grad = const_cast<float*>(g);
+    return DG_OK;
+}
+
+int clf_seeded_backward(dg_clf* h, const float* seed, int B, hipStream_t s, float** grad) {
+    int rc = clf_grow_gbuf(h, B);
+    if (rc) return rc;
+    return clf_backward_chain(h, seed, B, grad, s);
+}
+
+// d(sum_b CE(softmax(logits_b), y_b))/dx for x [B,H,W,C]; y = labels or, when NULL, the model's own prediction.
+static int clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float** grad_out, hipStream_t s) {
+    int rc = clf_kept_forward(h, x, B, s);
+    if (rc) return rc;
+    if ((rc = clf_grow_gbuf(h, B))) return rc;
+    clf_launch_ce_grad(h->acts[h->logit_layer], labels, h->gbuf[0], B, h->n_logits, s);
+    return clf_backward_chain(h, h->gbuf[0], B, grad_out, s);
+}
 
 extern "C" {
 
 int dg_clf_create(int device, int in_h, int in_w, int in_c, dg_clf** out) {
-    if (!out || in_h <= 0 || in_w <= 0 || in_c <= 0) return fail(DG_E_INVALID, "dg_clf_create: bad input shape");
+    if (!out || in_h <= 0 || in_w <= 0 || in_c <= 0) return clf_fail(DG_E_INVALID, "dg_clf_create: bad input shape");
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(DG_E_HIP, "no HIP device");
-    if (device < 0 || device >= n) return fail(DG_E_INVALID, "device %d out of range", device);
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return clf_fail(DG_E_HIP, "no HIP device");
+    if (device < 0 || device >= n) return clf_fail(DG_E_INVALID, "device %d out of range", device);
     dg_clf* h = new dg_clf();
     h->device = device;
     h->in_h = h->cur_h = in_h;
@@ -295,23 +363,23 @@ int dg_clf_destroy(dg_clf* h) {
         if (p) (void)hipFree(p);
     for (float* p : h->gbuf)
         if (p) (void)hipFree(p);
-    dg_cw_release(h->cw);
-    dg_train_release(h->tr);
+    cw_release(h->cw);
+    train_release(h->tr);
     delete h;
     return DG_OK;
 }
 
 int dg_clf_add_layer(dg_clf* h, int kind, int p0, int p1, int p2, int p3, int p4, int p5) {
-    if (!h) return fail(DG_E_INVALID, "null handle");
+    if (!h) return clf_fail(DG_E_INVALID, "null handle");
     CLF_TRY(hipSetDevice(h->device));
     ClfLayer l;
     l.kind = kind;
     l.ih = h->cur_h; l.iw = h->cur_w; l.ic = h->cur_c;
     switch (kind) {
-        case L_CONV: {
-            if (h->flat) return fail(DG_E_INVALID, "Conv2D after Flatten");
+        case DG_LAYER_CONV2D: {
+            if (h->flat) return clf_fail(DG_E_INVALID, "Conv2D after Flatten");
             l.cout = p0; l.kh = p1; l.kw = p2; l.sh = p3; l.sw = p4; l.same = p5; l.cin = h->cur_c;
-            if (l.cout <= 0 || l.kh <= 0 || l.kw <= 0 || l.sh <= 0 || l.sw <= 0) return fail(DG_E_INVALID, "bad Conv2D parameters");
+            if (l.cout <= 0 || l.kh <= 0 || l.kw <= 0 || l.sh <= 0 || l.sw <= 0) return clf_fail(DG_E_INVALID, "bad Conv2D parameters");
             if (l.same) {       // TF SAME: out = ceil(in / stride), pad_before = pad_total / 2
                 l.oh = (l.ih + l.sh - 1) / l.sh;
                 l.ow = (l.iw + l.sw - 1) / l.sw;
@@ -319,7 +387,7 @@ int dg_clf_add_layer(dg_clf* h, int kind, int p0, int p1, int p2, int p3, int p4
                 l.pad_t = pt / 2;
                 l.pad_l = pl / 2;
             } else {            // VALID
-                if (l.ih < l.kh || l.iw < l.kw) return fail(DG_E_INVALID, "VALID Conv2D kernel larger than its input");
+                if (l.ih < l.kh || l.iw < l.kw) return clf_fail(DG_E_INVALID, "VALID Conv2D kernel larger than its input");
                 l.oh = (l.ih - l.kh) / l.sh + 1;
                 l.ow = (l.iw - l.kw) / l.sw + 1;
             }
@@ -328,37 +396,43 @@ int dg_clf_add_layer(dg_clf* h, int kind, int p0, int p1, int p2, int p3, int p4
             CLF_TRY(hipMalloc(&l.b, (size_t)l.cout * sizeof(float)));
             break;
         }
-        case L_LINEAR: {
-            if (!h->flat) return fail(DG_E_INVALID, "Linear needs a Flatten before it");
+        case DG_LAYER_LINEAR: {
+            if (!h->flat) return clf_fail(DG_E_INVALID, "Linear needs a Flatten before it");
             l.cin = h->cur_c; l.cout = p0;
-            if (l.cout <= 0) return fail(DG_E_INVALID, "bad Linear width");
+            if (l.cout <= 0) return clf_fail(DG_E_INVALID, "bad Linear width");
             l.oh = l.ow = 1; l.oc = l.cout;
             CLF_TRY(hipMalloc(&l.W, (size_t)l.cin * l.cout * sizeof(float)));
             CLF_TRY(hipMalloc(&l.b, (size_t)l.cout * sizeof(float)));
             break;
         }
-        case L_FLATTEN:
+        case DG_LAYER_FLATTEN:
             l.oh = l.ow = 1; l.oc = l.ih * l.iw * l.ic; l.skip = true;       // NHWC row-major: a reshape, no data movement
             h->flat = true;
             break;
-        case L_RELU: case L_SOFTMAX: case L_DROPOUT:
+        case DG_LAYER_RELU: case DG_LAYER_SOFTMAX: case DG_LAYER_DROPOUT:
             l.oh = l.ih; l.ow = l.iw; l.oc = l.ic;
-            if (kind == L_DROPOUT) l.skip = true;                             // K.learning_phase() == 0 at evaluation
-            if (kind == L_RELU && !h->layers.empty()) {
+            if (kind == DG_LAYER_DROPOUT) l.skip = true;                             // K.learning_phase() == 0 at evaluation
+            if (kind == DG_LAYER_RELU && !h->layers.empty()) {
                 // fold the ReLU into the producing Conv2D / Linear (skipping identity layers in between)
                 for (int j = (int)h->layers.size() - 1; j >= 0; --j) {
                     ClfLayer& p = h->layers[j];
                     if (p.skip) continue;
-                    if ((p.kind == L_CONV || p.kind == L_LINEAR) && !p.fused_relu) { p.fused_relu = true; l.skip = true; }
+                    if (p.has_params() && !p.fused_relu) { p.fused_relu = true; l.skip = true; }
                     break;
                 }
             }
             break;
         default:
-            return fail(DG_E_INVALID, "unknown layer kind %d", kind);
+            return clf_fail(DG_E_INVALID, "unknown layer kind %d", kind);
     }
     h->cur_h = l.oh; h->cur_w = l.ow; h->cur_c = l.oc;
     h->layers.push_back(l);
+    if (kind == DG_LAYER_SOFTMAX) {
+        h->has_softmax = true;
+    } else if (!l.skip) {
+        h->logit_layer = (int)h->layers.size() - 1;
+        h->n_logits = (int)l.features();
+    }
     return (int)h->layers.size() - 1;
 }
 
@@ -366,23 +440,23 @@ int dg_clf_output_width(dg_clf* h) { return h ? h->cur_h * h->cur_w * h->cur_c :
 
 int dg_clf_set_weights(dg_clf* h, int layer, const float* W, const int64_t* wshape, int wndim, const float* b, int64_t blen,
                        int is_device) {
-    if (!h || !W || !b || !wshape) return fail(DG_E_INVALID, "null argument");
-    if (layer < 0 || layer >= (int)h->layers.size()) return fail(DG_E_INVALID, "layer %d out of range", layer);
+    if (!h || !W || !b || !wshape) return clf_fail(DG_E_INVALID, "null argument");
+    if (layer < 0 || layer >= (int)h->layers.size()) return clf_fail(DG_E_INVALID, "layer %d out of range", layer);
     ClfLayer& l = h->layers[layer];
     CLF_TRY(hipSetDevice(h->device));
     size_t n = 0;
-    if (l.kind == L_CONV) {
+    if (l.kind == DG_LAYER_CONV2D) {
         if (wndim != 4 || wshape[0] != l.kh || wshape[1] != l.kw || wshape[2] != l.cin || wshape[3] != l.cout)
-            return fail(DG_E_INVALID, "layer %d: Conv2D kernels must be [%d,%d,%d,%d]", layer, l.kh, l.kw, l.cin, l.cout);
+            return clf_fail(DG_E_INVALID, "layer %d: Conv2D kernels must be [%d,%d,%d,%d]", layer, l.kh, l.kw, l.cin, l.cout);
         n = (size_t)l.kh * l.kw * l.cin * l.cout;
-    } else if (l.kind == L_LINEAR) {
+    } else if (l.kind == DG_LAYER_LINEAR) {
         if (wndim != 2 || wshape[0] != l.cin || wshape[1] != l.cout)
-            return fail(DG_E_INVALID, "layer %d: Linear W must be [%d,%d]", layer, l.cin, l.cout);
+            return clf_fail(DG_E_INVALID, "layer %d: Linear W must be [%d,%d]", layer, l.cin, l.cout);
         n = (size_t)l.cin * l.cout;
     } else {
-        return fail(DG_E_INVALID, "layer %d has no parameters", layer);
+        return clf_fail(DG_E_INVALID, "layer %d has no parameters", layer);
     }
-    if (blen != l.cout) return fail(DG_E_INVALID, "layer %d: bias must have %d entries", layer, l.cout);
+    if (blen != l.cout) return clf_fail(DG_E_INVALID, "layer %d: bias must have %d entries", layer, l.cout);
     const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     CLF_TRY(hipMemcpy(l.W, W, n * sizeof(float), kind));
     CLF_TRY(hipMemcpy(l.b, b, (size_t)l.cout * sizeof(float), kind));
@@ -391,291 +465,78 @@ int dg_clf_set_weights(dg_clf* h, int layer, const float* W, const int64_t* wsha
 }
 
 int dg_clf_set_dropout(dg_clf* h, int layer, float keep_prob) {
-    if (!h) return fail(DG_E_INVALID, "null handle");
-    if (layer < 0 || layer >= (int)h->layers.size() || h->layers[layer].kind != L_DROPOUT)
-        return fail(DG_E_INVALID, "layer %d is not a Dropout layer", layer);
-    if (!(keep_prob > 0.f && keep_prob <= 1.f)) return fail(DG_E_INVALID, "Dropout keep_prob %g outside (0, 1]", (double)keep_prob);
+    if (!h) return clf_fail(DG_E_INVALID, "null handle");
+    if (layer < 0 || layer >= (int)h->layers.size() || h->layers[layer].kind != DG_LAYER_DROPOUT)
+        return clf_fail(DG_E_INVALID, "layer %d is not a Dropout layer", layer);
+    if (!(keep_prob > 0.f && keep_prob <= 1.f)) return clf_fail(DG_E_INVALID, "Dropout keep_prob %g outside (0, 1]", (double)keep_prob);
     h->layers[layer].keep_prob = keep_prob;
     return DG_OK;
 }
 
 int dg_clf_get_weights(dg_clf* h, int layer, float* W, float* b, int is_device) {
-    if (!h || !W || !b) return fail(DG_E_INVALID, "null argument");
-    if (layer < 0 || layer >= (int)h->layers.size()) return fail(DG_E_INVALID, "layer %d out of range", layer);
+    if (!h || !W || !b) return clf_fail(DG_E_INVALID, "null argument");
+    if (layer < 0 || layer >= (int)h->layers.size()) return clf_fail(DG_E_INVALID, "layer %d out of range", layer);
     const ClfLayer& l = h->layers[layer];
-    if (l.kind != L_CONV && l.kind != L_LINEAR) return fail(DG_E_INVALID, "layer %d has no parameters", layer);
-    if (!l.have_w) return fail(DG_E_STATE, "layer %d has no weights", layer);
+    if (!l.has_params()) return clf_fail(DG_E_INVALID, "layer %d has no parameters", layer);
+    if (!l.have_w) return clf_fail(DG_E_STATE, "layer %d has no weights", layer);
     CLF_TRY(hipSetDevice(h->device));
-    const size_t nw = l.kind == L_CONV ? (size_t)l.kh * l.kw * l.cin * l.cout : (size_t)l.cin * l.cout;
+    const size_t nw = l.kind == DG_LAYER_CONV2D ? (size_t)l.kh * l.kw * l.cin * l.cout : (size_t)l.cin * l.cout;
     const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     CLF_TRY(hipMemcpy(W, l.W, nw * sizeof(float), kind));
     CLF_TRY(hipMemcpy(b, l.b, (size_t)l.cout * sizeof(float), kind));
     return DG_OK;
 }
 
-static int clf_run(dg_clf* h, const float* x, int B, float* logits, float* probs, hipStream_t s, bool keep = false) {
-    for (size_t j = 0; j < h->layers.size(); ++j)
-        if ((h->layers[j].kind == L_CONV || h->layers[j].kind == L_LINEAR) && !h->layers[j].have_w)
-            return fail(DG_E_STATE, "classifier layer %d has no weights", (int)j);
-    size_t need = 0;
-    for (const auto& l : h->layers) need = std::max(need, (size_t)B * l.oh * l.ow * l.oc);
-    if (need > h->buf_floats) {
-        for (float*& p : h->buf) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-            CLF_TRY(hipMalloc(&p, need * sizeof(float)));
-        }
-        h->buf_floats = need;
-    }
-    // the logits are the output of the last parameterised layer ("logits" = layers[-2] when the model ends in Softmax,
-    // network_builder.py:148-153)
-    int last_param = -1, softmax_at = -1;
-    for (int j = 0; j < (int)h->layers.size(); ++j) {
-        if (h->layers[j].kind == L_SOFTMAX) softmax_at = j;
-        if (!h->layers[j].skip && h->layers[j].kind != L_SOFTMAX) last_param = j;
-    }
-    if (last_param < 0) return fail(DG_E_STATE, "classifier has no layers");
-    const float* cur = x;
-    int which = 0;
-    for (int j = 0; j < (int)h->layers.size(); ++j) {
-        const ClfLayer& l = h->layers[j];
-        if (l.skip || l.kind == L_SOFTMAX) continue;
-        const long long total = (long long)B * l.oh * l.ow * l.oc;
-        float* out = (j == last_param && logits) ? logits : h->buf[which];
-        if (keep) {                                      // the gradient path needs every layer's output afterwards
-            if (h->acts.size() < h->layers.size()) { h->acts.resize(h->layers.size(), nullptr); h->acts_floats.resize(h->layers.size(), 0); }
-            if ((size_t)total > h->acts_floats[j]) {
-                if (h->acts[j]) (void)hipFree(h->acts[j]);
-                h->acts[j] = nullptr;
-                CLF_TRY(hipMalloc(&h->acts[j], (size_t)total * sizeof(float)));
-                h->acts_floats[j] = (size_t)total;
-            }
-            out = h->acts[j];
-        }
-        const unsigned grid = (unsigned)((total + 255) / 256);
-        if (l.kind == L_CONV)
-            hipLaunchKernelGGL(clf_conv2d_kernel, dim3(grid), dim3(256), 0, s, cur, l.W, l.b, out, total, l.ih, l.iw, l.ic, l.oh,
-                               l.ow, l.oc, l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
-        else if (l.kind == L_LINEAR)
-            hipLaunchKernelGGL(clf_linear_kernel, dim3(grid), dim3(256), 0, s, cur, l.W, l.b, out, total, l.cin, l.cout,
-                               l.fused_relu ? 1 : 0);
-        else
-            hipLaunchKernelGGL(clf_relu_kernel, dim3(grid), dim3(256), 0, s, cur, out, total);
-        cur = out;
-        which ^= 1;
-    }
-    h->n_out = h->layers[last_param].oh * h->layers[last_param].ow * h->layers[last_param].oc;
-    if (probs) {
-        if (softmax_at >= 0)
-            hipLaunchKernelGGL(clf_softmax_kernel, dim3((B + 63) / 64), dim3(64), 0, s, cur, probs, B, h->n_out);
-        else
-            CLF_TRY(hipMemcpyAsync(probs, cur, (size_t)B * h->n_out * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    CLF_TRY(hipGetLastError());
-    return DG_OK;
-}
-
 int dg_clf_forward(dg_clf* h, const float* x, int B, float* logits, float* probs, void* stream) {
-    if (!h || !x || B <= 0) return fail(DG_E_INVALID, "dg_clf_forward: bad argument");
+    if (!h || !x || B <= 0) return clf_fail(DG_E_INVALID, "dg_clf_forward: bad argument");
     CLF_TRY(hipSetDevice(h->device));
     return clf_run(h, x, B, logits, probs, (hipStream_t)stream);
 }
 
 int dg_eval_batch(dg_clf* h, const float* rec, const float* orig, const int32_t* labels, int B, int32_t* preds, float* diffs,
                   int32_t* n_correct, void* stream) {
-    if (!h || !rec || B <= 0) return fail(DG_E_INVALID, "dg_eval_batch: bad argument");
+    if (!h || !rec || B <= 0) return clf_fail(DG_E_INVALID, "dg_eval_batch: bad argument");
     CLF_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     const int ncls = dg_clf_output_width(h);
-    if ((size_t)B * ncls > h->scores_floats) {
-        if (h->scores) (void)hipFree(h->scores);
-        h->scores = nullptr;
-        CLF_TRY(hipMalloc(&h->scores, (size_t)B * ncls * sizeof(float)));
-        h->scores_floats = (size_t)B * ncls;
-    }
-    float* scratch = h->scores;
-    int rc = clf_run(h, rec, B, scratch, nullptr, s);      // argmax(probs) == argmax(logits): softmax is monotone
+    int rc = clf_grow(&h->scores, 1, h->scores_floats, (size_t)B * ncls);
     if (rc) return rc;
-    const int P = h->in_h * h->in_w * h->in_c;
-    hipLaunchKernelGGL(clf_eval_kernel, dim3(B), dim3(256), 0, s, scratch, ncls, rec, orig, P, labels, preds, diffs, n_correct);
+    if ((rc = clf_run(h, rec, B, h->scores, nullptr, s))) return rc;      // argmax(probs) == argmax(logits): softmax is monotone
+    hipLaunchKernelGGL(clf_eval_kernel, dim3(B), dim3(256), 0, s, h->scores, ncls, rec, orig, h->pixels(), labels, preds, diffs, n_correct);
     CLF_TRY(hipGetLastError());
     return DG_OK;
-}
-
-static int clf_last_layer(const dg_clf* h) {
-    int last = -1;
-    for (int j = 0; j < (int)h->layers.size(); ++j)
-        if (!h->layers[j].skip && h->layers[j].kind != L_SOFTMAX) last = j;
-    return last;
-}
-
-static int clf_grow_gbuf(dg_clf* h, int B) {
-    size_t need = (size_t)B * h->in_h * h->in_w * h->in_c;
-    for (const auto& l : h->layers) need = std::max(need, (size_t)B * l.oh * l.ow * l.oc);
-    if (need > h->gbuf_floats) {
-        for (float*& p : h->gbuf) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-            CLF_TRY(hipMalloc(&p, need * sizeof(float)));
-        }
-        h->gbuf_floats = need;
-    }
-    return DG_OK;
-}
-
-// The seed-agnostic chain: g = seed [B, n] = dLoss/dlogits -> dLoss/dx, through the layer outputs the last
-// clf_run(keep = true) left in h->acts.  The result lies in one of the gbuf ping-pong buffers (never in `seed`).
-static int clf_backward_chain(dg_clf* h, const float* seed, int B, float** grad_out, hipStream_t s) {
-    const int last = clf_last_layer(h);
-    int which = 0;
-    const float* g = seed;
-    for (int j = last; j >= 0; --j) {
-        const ClfLayer& l = h->layers[j];
-        if (l.skip || l.kind == L_SOFTMAX) continue;
-        const long long total = (long long)B * l.ih * l.iw * l.ic;
-        float* dx = h->gbuf[which ^ 1];
-        const unsigned grid = (unsigned)((total + 255) / 256);
-        if (l.kind == L_LINEAR)
-            hipLaunchKernelGGL(clf_linear_bwd_kernel, dim3(grid), dim3(256), 0, s, g, h->acts[j], l.W, dx, total, l.cin, l.cout,
-                               l.fused_relu ? 1 : 0);
-        else if (l.kind == L_CONV)
-            hipLaunchKernelGGL(clf_conv2d_bwd_kernel, dim3(grid), dim3(256), 0, s, g, h->acts[j], l.W, dx, total, l.ih, l.iw, l.ic,
-                               l.oh, l.ow, l.oc, l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
-        else
-            hipLaunchKernelGGL(clf_relu_bwd_kernel, dim3(grid), dim3(256), 0, s, g, h->acts[j], dx, total);
-        which ^= 1;
-        g = dx;
-    }
-    CLF_TRY(hipGetLastError());
-    *grad_out = const_cast<float*>(g);
-    return DG_OK;
-}
-
-// d(sum_b CE(softmax(logits_b), y_b))/dx for x [B,H,W,C]; y = labels or, when NULL, the model's own prediction.
-static int clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float** grad_out, hipStream_t s) {
-    int rc = clf_run(h, x, B, nullptr, nullptr, s, /*keep=*/true);
-    if (rc) return rc;
-    if ((rc = clf_grow_gbuf(h, B))) return rc;
-    const int last = clf_last_layer(h);
-    const int n = h->layers[last].oh * h->layers[last].ow * h->layers[last].oc;
-    float* g = h->gbuf[0];
-    hipLaunchKernelGGL(clf_ce_grad_kernel, dim3((B + 63) / 64), dim3(64), 0, s, h->acts[last], labels, g, B, n);
-    return clf_backward_chain(h, g, B, grad_out, s);
-}
-
-// ---- library-internal entries of the Carlini-Wagner attack (dg_cw.hip) ------------------------------------------------
-// Forward of x [B, ...] keeping every layer's output; *logits = the kept logits [B, n] (valid until the next clf_run).
-__attribute__((visibility("hidden"))) int dg_clf_kept_forward(dg_clf* h, const float* x, int B, hipStream_t s,
-                                                              const float** logits) {
-    int rc = clf_run(h, x, B, nullptr, nullptr, s, /*keep=*/true);
-    if (rc) return rc;
-    *logits = h->acts[clf_last_layer(h)];
-    return DG_OK;
-}
-
-// dLoss/dx from the seed dLoss/dlogits [B, n] after dg_clf_kept_forward of the same B images.
-__attribute__((visibility("hidden"))) int dg_clf_seeded_backward(dg_clf* h, const float* seed, int B, hipStream_t s, float** grad) {
-    int rc = clf_grow_gbuf(h, B);
-    if (rc) return rc;
-    return clf_backward_chain(h, seed, B, grad, s);
-}
-
-// device, pixels per image, class count (0 before the model is complete) and the CW workspace slot
-__attribute__((visibility("hidden"))) CwWork** dg_clf_cw_slot(dg_clf* h, int* device, int* P, int* n) {
-    *device = h->device;
-    *P = h->in_h * h->in_w * h->in_c;
-    const int last = clf_last_layer(h);
-    *n = last < 0 ? 0 : h->layers[last].oh * h->layers[last].ow * h->layers[last].oc;
-    return &h->cw;
-}
-
-// ---- library-internal entries of the training path (dg_clf_train.hip, dg_clf_internal.h) ------------------------------
-__attribute__((visibility("hidden"))) int dg_clf_layer_count(const dg_clf* h) { return (int)h->layers.size(); }
-
-__attribute__((visibility("hidden"))) void dg_clf_layer_view(const dg_clf* h, int j, DgClfLayerView* v) {
-    const ClfLayer& l = h->layers[j];
-    *v = DgClfLayerView{l.kind, l.ih, l.iw, l.ic, l.oh, l.ow, l.oc, l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l,
-                        l.fused_relu ? 1 : 0, l.skip ? 1 : 0, l.keep_prob, l.W, l.b};
-}
-
-__attribute__((visibility("hidden"))) TrainWork** dg_clf_train_slot(dg_clf* h, int* device, int* P, int* have_weights) {
-    *device = h->device;
-    *P = h->in_h * h->in_w * h->in_c;
-    *have_weights = 1;
-    for (const auto& l : h->layers)
-        if ((l.kind == L_CONV || l.kind == L_LINEAR) && !l.have_w) *have_weights = 0;
-    return &h->tr;
-}
-
-__attribute__((visibility("hidden"))) void dg_clf_launch_forward(const dg_clf* h, int j, const float* in, float* out, int B, hipStream_t s) {
-    const ClfLayer& l = h->layers[j];
-    const long long total = (long long)B * l.oh * l.ow * l.oc;
-    const unsigned grid = (unsigned)((total + 255) / 256);
-    if (l.kind == L_CONV)
-        hipLaunchKernelGGL(clf_conv2d_kernel, dim3(grid), dim3(256), 0, s, in, l.W, l.b, out, total, l.ih, l.iw, l.ic, l.oh, l.ow,
-                           l.oc, l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
-    else if (l.kind == L_LINEAR)
-        hipLaunchKernelGGL(clf_linear_kernel, dim3(grid), dim3(256), 0, s, in, l.W, l.b, out, total, l.cin, l.cout, l.fused_relu ? 1 : 0);
-    else
-        hipLaunchKernelGGL(clf_relu_kernel, dim3(grid), dim3(256), 0, s, in, out, total);
-}
-
-__attribute__((visibility("hidden"))) void dg_clf_launch_input_grad(const dg_clf* h, int j, const float* g, const float* out, float* dx, int B,
-                                                                    hipStream_t s) {
-    const ClfLayer& l = h->layers[j];
-    const long long total = (long long)B * l.ih * l.iw * l.ic;
-    const unsigned grid = (unsigned)((total + 255) / 256);
-    if (l.kind == L_LINEAR)
-        hipLaunchKernelGGL(clf_linear_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, l.W, dx, total, l.cin, l.cout, l.fused_relu ? 1 : 0);
-    else if (l.kind == L_CONV)
-        hipLaunchKernelGGL(clf_conv2d_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, l.W, dx, total, l.ih, l.iw, l.ic, l.oh, l.ow, l.oc,
-                           l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
-    else
-        hipLaunchKernelGGL(clf_relu_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, dx, total);
-}
-
-__attribute__((visibility("hidden"))) void dg_clf_launch_ce_grad(const float* logits, const int32_t* labels, float* g, int B, int n, hipStream_t s) {
-    hipLaunchKernelGGL(clf_ce_grad_kernel, dim3((B + 63) / 64), dim3(64), 0, s, logits, labels, g, B, n);
-}
-
-__attribute__((visibility("hidden"))) void dg_clf_launch_fgsm(const float* x, const float* grad, float* xadv, long long total, float eps, float lo,
-                                                              float hi, hipStream_t s) {
-    hipLaunchKernelGGL(clf_fgsm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, grad, xadv, total, eps, lo, hi);
 }
 
 int dg_clf_input_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float* grad, void* stream) {
-    if (!h || !x || !grad || B <= 0) return fail(DG_E_INVALID, "dg_clf_input_gradient: bad argument");
+    if (!h || !x || !grad || B <= 0) return clf_fail(DG_E_INVALID, "dg_clf_input_gradient: bad argument");
     CLF_TRY(hipSetDevice(h->device));
     float* g = nullptr;
     int rc = clf_input_gradient(h, x, labels, B, &g, (hipStream_t)stream);
     if (rc) return rc;
-    CLF_TRY(hipMemcpyAsync(grad, g, (size_t)B * h->in_h * h->in_w * h->in_c * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    CLF_TRY(hipMemcpyAsync(grad, g, (size_t)B * h->pixels() * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return DG_OK;
 }
 
 int dg_clf_backward(dg_clf* h, const float* x, const float* dlogits, int B, float* grad, void* stream) {
-    if (!h || !x || !dlogits || !grad || B <= 0) return fail(DG_E_INVALID, "dg_clf_backward: bad argument");
+    if (!h || !x || !dlogits || !grad || B <= 0) return clf_fail(DG_E_INVALID, "dg_clf_backward: bad argument");
     CLF_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    int rc = clf_run(h, x, B, nullptr, nullptr, s, /*keep=*/true);
-    if (rc) return rc;
-    if ((rc = clf_grow_gbuf(h, B))) return rc;
     float* g = nullptr;
-    if ((rc = clf_backward_chain(h, dlogits, B, &g, s))) return rc;
-    CLF_TRY(hipMemcpyAsync(grad, g, (size_t)B * h->in_h * h->in_w * h->in_c * sizeof(float), hipMemcpyDeviceToDevice, s));
+    int rc = clf_kept_forward(h, x, B, s);
+    if (rc || (rc = clf_seeded_backward(h, dlogits, B, s, &g))) return rc;
+    CLF_TRY(hipMemcpyAsync(grad, g, (size_t)B * h->pixels() * sizeof(float), hipMemcpyDeviceToDevice, s));
     return DG_OK;
 }
 
 int dg_fgsm(dg_clf* h, const float* x, const int32_t* labels, int B, float eps, float clip_min, float clip_max, float* x_adv,
             void* stream) {
-    if (!h || !x || !x_adv || B <= 0) return fail(DG_E_INVALID, "dg_fgsm: bad argument");
+    if (!h || !x || !x_adv || B <= 0) return clf_fail(DG_E_INVALID, "dg_fgsm: bad argument");
     CLF_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     float* g = nullptr;
     int rc = clf_input_gradient(h, x, labels, B, &g, s);
     if (rc) return rc;
-    const long long total = (long long)B * h->in_h * h->in_w * h->in_c;
-    hipLaunchKernelGGL(clf_fgsm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, g, x_adv, total, eps, clip_min, clip_max);
+    clf_launch_fgsm(x, g, x_adv, (long long)B * h->pixels(), eps, clip_min, clip_max, s);
     CLF_TRY(hipGetLastError());
     return DG_OK;
 }

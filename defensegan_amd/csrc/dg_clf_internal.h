@@ -1,40 +1,105 @@
-// Library-internal view of a classifier handle (dg_clf.hip) for the training path (dg_clf_train.hip): the layer geometry and
-// parameter pointers, and launchers of dg_clf.hip's own forward / input-gradient kernels, so that training reuses them unchanged.
+// The classifier handle as its three source files see it: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
+// dg_cw.hip (the Carlini-Wagner attack) and dg_clf_train.hip (training).  Everything here is internal to the library: plain C++
+// under hidden visibility, nothing of it is exported.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 #include "../../include/defensegan_hip.h"
 
-struct TrainWork;
+extern "C" __attribute__((visibility("hidden"))) void dg_set_error_message(const char* msg);   // dg_engine.cpp (dg_last_error storage)
 
-struct DgClfLayerView {
-    int kind;                      // DG_LAYER_*
-    int ih, iw, ic, oh, ow, oc;    // per-image input / output shapes (flat layers: h = w = 1)
-    int kh, kw, sh, sw, pad_t, pad_l;
-    int fused_relu;                // the following ReLU is applied in this layer's kernel
-    int skip;                      // no kernel at evaluation (Flatten, Dropout, a folded ReLU)
-    float keep_prob;               // Dropout: the reference's Dropout(prob) (0 = never set)
-    float* W;                      // Conv2D kernels [kh,kw,ic,oc] / Linear W [ic,oc], device
-    float* b;                      // bias [oc], device
+#pragma GCC visibility push(hidden)
+
+// One layer; its kind is a DG_LAYER_* of the public header.
+struct ClfLayer {
+    int kind = 0;
+    // conv
+    int kh = 0, kw = 0, sh = 1, sw = 1, same = 0, cin = 0, cout = 0, pad_t = 0, pad_l = 0;
+    // shapes (per image; flat layers: h = w = 1)
+    int ih = 0, iw = 0, ic = 0, oh = 0, ow = 0, oc = 0;
+    bool fused_relu = false;     // the ReLU that follows is applied in this layer's kernel
+    bool skip = false;           // no kernel at evaluation: a ReLU folded into its predecessor / identity layers
+    float* W = nullptr;          // Conv2D kernels [kh,kw,cin,cout] / Linear W [cin,cout], device
+    float* b = nullptr;          // bias [cout], device
+    bool have_w = false;
+    float keep_prob = 0.f;       // Dropout: the reference's Dropout(prob), used by the training phase only (0 = never set)
+
+    bool has_params() const { return kind == DG_LAYER_CONV2D || kind == DG_LAYER_LINEAR; }
+    long long features() const { return (long long)oh * ow * oc; }
 };
 
-extern "C" {
-__attribute__((visibility("hidden"))) int dg_clf_layer_count(const dg_clf* h);
-__attribute__((visibility("hidden"))) void dg_clf_layer_view(const dg_clf* h, int j, DgClfLayerView* v);
-// device, pixels per image, whether every Conv2D / Linear layer has weights, and the training workspace slot
-__attribute__((visibility("hidden"))) TrainWork** dg_clf_train_slot(dg_clf* h, int* device, int* P, int* have_weights);
-// layer j's evaluation kernel (Conv2D / Linear with its fused ReLU, or an unfused ReLU): in [B, ih, iw, ic] -> out [B, oh, ow, oc]
-__attribute__((visibility("hidden"))) void dg_clf_launch_forward(const dg_clf* h, int j, const float* in, float* out, int B, hipStream_t s);
-// layer j's input gradient as dg_clf_input_gradient computes it: dx = d/din of sum(g * out), out = the layer's kept output
-__attribute__((visibility("hidden"))) void dg_clf_launch_input_grad(const dg_clf* h, int j, const float* g, const float* out, float* dx, int B,
-                                                                    hipStream_t s);
-// dCE/dlogits with the label or (labels == NULL) the model's own first argmax, as dg_fgsm seeds its backward
-__attribute__((visibility("hidden"))) void dg_clf_launch_ce_grad(const float* logits, const int32_t* labels, float* g, int B, int n, hipStream_t s);
-// x_adv = clip(x + eps * sign(grad), lo, hi), dg_fgsm's last kernel
-__attribute__((visibility("hidden"))) void dg_clf_launch_fgsm(const float* x, const float* grad, float* xadv, long long total, float eps, float lo,
-                                                              float hi, hipStream_t s);
-__attribute__((visibility("hidden"))) void dg_train_release(TrainWork* w);    // dg_clf_train.hip
+struct CwWork;       // dg_cw.hip
+struct TrainWork;    // dg_clf_train.hip
+
+struct dg_clf {
+    int device = 0;
+    int in_h = 0, in_w = 0, in_c = 0;
+    std::vector<ClfLayer> layers;
+    int cur_h = 0, cur_w = 0, cur_c = 0;      // running shape while layers are added (flat: h = w = 1, c = width)
+    bool flat = false;
+    // the logits are the output of the last layer that runs a kernel other than Softmax ("logits" = layers[-2] when the model
+    // ends in Softmax, network_builder.py:148-153); kept up to date as layers are added
+    int logit_layer = -1;
+    int n_logits = 0;
+    bool has_softmax = false;
+    float* buf[2] = {nullptr, nullptr};
+    size_t buf_floats = 0;
+    float* scores = nullptr;                  // [B, n_out] scratch of dg_eval_batch
+    size_t scores_floats = 0;
+    std::vector<float*> acts;                 // per-layer outputs kept by the gradient path
+    std::vector<size_t> acts_floats;
+    float* gbuf[2] = {nullptr, nullptr};      // gradient ping-pong
+    size_t gbuf_floats = 0;
+    CwWork* cw = nullptr;                     // Carlini-Wagner workspace, grown on demand
+    TrainWork* tr = nullptr;                  // training workspace and Adam state
+
+    int pixels() const { return in_h * in_w * in_c; }
+};
+
+// ---- errors ---------------------------------------------------------------------------------------------------------------------
+int clf_fail(int code, const char* fmt, ...);      // sets dg_last_error's message, returns code
+
+#define CLF_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) return clf_fail(DG_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));        \
+    } while (0)
+
+// Device buffers that only grow: when `need` elements exceed the capacity `cap` that the n buffers p[0..n) share, each is freed
+// and allocated anew with exactly `need` elements.
+template <class T>
+int clf_grow(T** p, int n, size_t& cap, size_t need) {
+    if (need <= cap) return DG_OK;
+    cap = 0;
+    for (int i = 0; i < n; ++i) {
+        if (p[i]) (void)hipFree(p[i]);
+        p[i] = nullptr;
+        CLF_TRY(hipMalloc(&p[i], need * sizeof(T)));
+    }
+    cap = need;
+    return DG_OK;
 }
+
+// ---- dg_clf.hip -----------------------------------------------------------------------------------------------------------------
+int clf_missing_weights(const dg_clf* h);          // the first Conv2D / Linear layer without weights, or -1
+// layer j's evaluation kernel (Conv2D / Linear with its fused ReLU, or an unfused ReLU): in [B, ih, iw, ic] -> out [B, oh, ow, oc]
+void clf_launch_forward(const dg_clf* h, int j, const float* in, float* out, int B, hipStream_t s);
+// layer j's input gradient: dx = d/din of sum(g * out), out = the layer's kept output
+void clf_launch_input_grad(const dg_clf* h, int j, const float* g, const float* out, float* dx, int B, hipStream_t s);
+// dCE/dlogits with the label or (labels == NULL) the model's own first argmax
+void clf_launch_ce_grad(const float* logits, const int32_t* labels, float* g, int B, int n, hipStream_t s);
+// x_adv = clip(x + eps * sign(grad), lo, hi)
+void clf_launch_fgsm(const float* x, const float* grad, float* xadv, long long total, float eps, float lo, float hi, hipStream_t s);
+// Forward of x [B, ...] keeping every layer's output in h->acts; the logits are h->acts[h->logit_layer] until the next forward.
+int clf_kept_forward(dg_clf* h, const float* x, int B, hipStream_t s);
+// dLoss/dx from the seed dLoss/dlogits [B, n] after clf_kept_forward of the same B images; *grad lies in h->gbuf, never in seed.
+int clf_seeded_backward(dg_clf* h, const float* seed, int B, hipStream_t s, float** grad);
+
+void cw_release(CwWork* w);          // dg_cw.hip
+void train_release(TrainWork* w);    // dg_clf_train.hip
+
+#pragma GCC visibility pop

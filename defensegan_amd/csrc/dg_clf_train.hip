@@ -17,23 +17,19 @@
 //   Adam           TF's, as in dg_cw.hip: m = 0.9 m + 0.1 g, v = 0.999 v + 0.001 g^2, p -= lr_t * m / (sqrt(v) + 1e-8),
 //                  lr_t = lr sqrt(1 - 0.999^t) / (1 - 0.9^t), t counted from 1 and held in the handle with m and v
 //
-// The forward and input-gradient kernels are dg_clf.hip's own, launched through its hidden helpers (dg_clf_internal.h), so that the
-// inner FGSM of a model without Dropout is dg_fgsm bit for bit.  New here: the weight gradients (tr_wgrad_kernel, an implicit GEMM
+// The forward and input-gradient kernels are dg_clf.hip's own, launched through the launchers its own walkers use
+// (dg_clf_internal.h), so that the inner FGSM of a model without Dropout is dg_fgsm bit for bit.  New here: the weight gradients (tr_wgrad_kernel, an implicit GEMM
 // whose reduction axis B*OH*OW is split over fixed slots of workgroups), the slot reduction fused with Adam (tr_reduce_adam_kernel),
 // Dropout, the cross-entropy seed and the loss.  No floating-point atomics: every sum has a fixed order, training is bit-reproducible.
 // gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <vector>
 
 #include "dg_clf_internal.h"
-
-extern "C" __attribute__((visibility("hidden"))) void dg_set_error_message(const char* msg);    // dg_engine.cpp
+#include "dg_shared_math.h"
 
 struct TrainWork {
     int cap_B = 0;
@@ -53,38 +49,6 @@ struct TrainWork {
 
 namespace {
 
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    dg_set_error_message(buf);
-    return code;
-}
-
-#define TR_TRY(expr)                                                                                \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return fail(DG_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
-
-// ---- Philox4x32-10 (the generator of dg_small.hip's latents, other counters) -------------------------------------------------
-__device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
 // Training-phase Dropout over [total] elements, four per thread: mask = floor(keep + u), y = (x / keep) * mask (x == NULL: mask only)
 __global__ __launch_bounds__(256) void tr_dropout_kernel(const float* __restrict__ x, float* __restrict__ y, float* __restrict__ mask,
                                                           long long total, float keep, uint32_t k0, uint32_t k1, uint32_t c1,
@@ -93,7 +57,7 @@ __global__ __launch_bounds__(256) void tr_dropout_kernel(const float* __restrict
     const long long first = q * 4;
     if (first >= total) return;
     uint32_t c[4] = {(uint32_t)q, c1, c2, c3};
-    philox10(c, k0, k1);
+    dg_philox4x32_10(c, k0, k1);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const long long i = first + r;
@@ -258,32 +222,33 @@ __global__ __launch_bounds__(256) void tr_reduce_adam_kernel(const float* __rest
     for (int z = 0; z < slots; ++z) g += part[(long long)z * per + e];
     if (grads) grads[e] = g;
     if (!m) return;
-    const float mm = 0.9f * m[e] + 0.1f * g;
-    const float vv = 0.999f * v[e] + 0.001f * (g * g);
-    m[e] = mm;
-    v[e] = vv;
     float* p = e < nW ? W + e : bias + (e - nW);
-    *p = *p - lr_t * mm / (sqrtf(vv) + 1e-8f);
+    *p = *p - dg_tf_adam_step(m[e], v[e], g, lr_t);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
+// What training derives from the handle's layers (read in place, h->layers): the layer whose output is the logits, the first
+// parameterised layer (nothing below it needs a gradient) and the Conv2D / Linear layers in order.
 struct Plan {
-    std::vector<DgClfLayerView> L;
-    int last = -1, first_param = -1, n = 0, P = 0, device = 0;
-    std::vector<int> params;                  // layer indices of Conv2D / Linear, in order
+    int last = -1, first_param = -1;
+    std::vector<int> params;
 };
 
-bool has_params(const DgClfLayerView& v) { return v.kind == DG_LAYER_CONV2D || v.kind == DG_LAYER_LINEAR; }
-bool has_output(const DgClfLayerView& v) { return has_params(v) || v.kind == DG_LAYER_DROPOUT || (v.kind == DG_LAYER_RELU && !v.skip); }
-long long features(const DgClfLayerView& v) { return (long long)v.oh * v.ow * v.oc; }
+// a layer that writes an output in the training phase (Dropout does, other than at evaluation)
+bool has_output(const ClfLayer& v) { return v.has_params() || v.kind == DG_LAYER_DROPOUT || (v.kind == DG_LAYER_RELU && !v.skip); }
 
-WGeo geometry(const DgClfLayerView& v, int B) {
+WGeo geometry(const ClfLayer& v, int B) {
     WGeo q;
     if (v.kind == DG_LAYER_CONV2D)
         q = WGeo{v.ih, v.iw, v.ic, v.oh, v.ow, v.kh, v.kw, v.sh, v.sw, v.pad_t, v.pad_l, v.kh * v.kw * v.ic, v.oc, B * v.oh * v.ow, 0};
     else
         q = WGeo{1, 1, v.ic * v.ih * v.iw, 1, 1, 1, 1, 1, 1, 0, 0, v.ic * v.ih * v.iw, v.oc, B, 0};
     return q;
+}
+
+size_t param_floats(const ClfLayer& v) {      // (W; b) of a Conv2D / Linear layer
+    const WGeo q = geometry(v, 1);
+    return (size_t)(q.M + 1) * q.N;
 }
 
 // slots of the reduction axis: about 1024 workgroups per layer (four per CU), at least 64 terms per slot, at most 256 slots
@@ -297,57 +262,46 @@ void slot_plan(const WGeo& q, int* slots, int* kc) {
     *slots = (int)((q.K + Kc - 1) / Kc);
 }
 
-int plan_of(dg_clf* h, Plan* p, TrainWork*** slot) {
-    int hw = 0;
-    *slot = dg_clf_train_slot(h, &p->device, &p->P, &hw);
-    const int cnt = dg_clf_layer_count(h);
-    p->L.resize(cnt);
+int plan_of(const dg_clf* h, Plan* p) {
+    const int cnt = (int)h->layers.size();
+    p->last = h->logit_layer;
+    for (int j = 0; j < cnt; ++j)
+        if (h->layers[j].has_params()) p->params.push_back(j);
+    if (p->last < 0 || p->params.empty()) return clf_fail(DG_E_STATE, "classifier has no parameterised layers");
+    p->first_param = p->params.front();
+    if (clf_missing_weights(h) >= 0) return clf_fail(DG_E_STATE, "classifier weights not set");
     for (int j = 0; j < cnt; ++j) {
-        dg_clf_layer_view(h, j, &p->L[j]);
-        if (has_output(p->L[j]) && p->L[j].kind != DG_LAYER_DROPOUT) p->last = j;
-        if (has_params(p->L[j])) {
-            if (p->first_param < 0) p->first_param = j;
-            p->params.push_back(j);
-        }
-    }
-    if (p->last < 0 || p->params.empty()) return fail(DG_E_STATE, "classifier has no parameterised layers");
-    if (!hw) return fail(DG_E_STATE, "classifier weights not set");
-    for (int j = 0; j < cnt; ++j) {
-        const DgClfLayerView& v = p->L[j];
+        const ClfLayer& v = h->layers[j];
         if (v.kind != DG_LAYER_DROPOUT) continue;
-        if (!(v.keep_prob > 0.f)) return fail(DG_E_STATE, "Dropout layer %d has no keep_prob (dg_clf_set_dropout)", j);
-        if (j > p->last) return fail(DG_E_INVALID, "Dropout layer %d after the logits is not supported in training", j);
+        if (!(v.keep_prob > 0.f)) return clf_fail(DG_E_STATE, "Dropout layer %d has no keep_prob (dg_clf_set_dropout)", j);
+        if (j > p->last) return clf_fail(DG_E_INVALID, "Dropout layer %d after the logits is not supported in training", j);
     }
-    const DgClfLayerView& l = p->L[p->last];
-    p->n = (int)features(l);
     return DG_OK;
 }
 
-int grow(float*& ptr, size_t floats) {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    TR_TRY(hipMalloc(&ptr, std::max<size_t>(floats, 1) * sizeof(float)));
-    return DG_OK;
+// a buffer that follows cap_B (or is allocated once): it has no capacity of its own and is always allocated anew
+template <class T>
+int regrow(T*& ptr, size_t count) {
+    size_t none = 0;
+    return clf_grow(&ptr, 1, none, count);
 }
 
 // the workspace for batches of up to B images, and the Adam state (zero, t = 0) on first use
-int ensure(TrainWork* w, const Plan& p, int B) {
-    const int cnt = (int)p.L.size();
+int ensure(const dg_clf* h, TrainWork* w, const Plan& p, int B) {
+    const int cnt = (int)h->layers.size();
+    int rc;
     if ((int)w->m.size() != cnt) {
         w->m.assign(cnt, nullptr);
         w->v.assign(cnt, nullptr);
         for (int j : p.params) {
-            const WGeo q = geometry(p.L[j], 1);
-            const size_t per = (size_t)(q.M + 1) * q.N;
-            int rc;
-            if ((rc = grow(w->m[j], per)) || (rc = grow(w->v[j], per))) return rc;
-            TR_TRY(hipMemset(w->m[j], 0, per * sizeof(float)));
-            TR_TRY(hipMemset(w->v[j], 0, per * sizeof(float)));
+            const size_t per = param_floats(h->layers[j]);
+            if ((rc = regrow(w->m[j], per)) || (rc = regrow(w->v[j], per))) return rc;
+            CLF_TRY(hipMemset(w->m[j], 0, per * sizeof(float)));
+            CLF_TRY(hipMemset(w->v[j], 0, per * sizeof(float)));
         }
         w->t = 0;
     }
     if (B <= w->cap_B) return DG_OK;
-    int rc;
     w->act.resize(cnt, nullptr);
     w->mask.resize(cnt, nullptr);
     w->in.assign(cnt, nullptr);
@@ -355,37 +309,31 @@ int ensure(TrainWork* w, const Plan& p, int B) {
     w->part_floats.resize(cnt, 0);
     w->slots.resize(cnt, 0);
     w->kc.resize(cnt, 0);
-    size_t widest = (size_t)p.P;
+    const size_t P = (size_t)h->pixels();
+    size_t widest = P;
     for (int j = 0; j < cnt; ++j) {
-        const DgClfLayerView& v = p.L[j];
-        widest = std::max(widest, (size_t)features(v));
-        if (has_output(v) && (rc = grow(w->act[j], (size_t)B * features(v)))) return rc;
-        if (v.kind == DG_LAYER_DROPOUT && (rc = grow(w->mask[j], (size_t)B * features(v)))) return rc;
+        const ClfLayer& v = h->layers[j];
+        widest = std::max(widest, (size_t)v.features());
+        if (has_output(v) && (rc = regrow(w->act[j], (size_t)B * v.features()))) return rc;
+        if (v.kind == DG_LAYER_DROPOUT && (rc = regrow(w->mask[j], (size_t)B * v.features()))) return rc;
     }
     for (float*& g : w->gbuf)
-        if ((rc = grow(g, (size_t)B * widest))) return rc;
-    if ((rc = grow(w->xb, (size_t)B * p.P)) || (rc = grow(w->xadv, (size_t)B * p.P)) || (rc = grow(w->seed, (size_t)B * p.n)) ||
-        (rc = grow(w->ce, 2 * (size_t)B)) || (rc = grow(w->loss, 1)))
+        if ((rc = regrow(g, (size_t)B * widest))) return rc;
+    if ((rc = regrow(w->xb, (size_t)B * P)) || (rc = regrow(w->xadv, (size_t)B * P)) || (rc = regrow(w->seed, (size_t)B * h->n_logits)) ||
+        (rc = regrow(w->ce, 2 * (size_t)B)) || (rc = regrow(w->loss, 1)) || (rc = regrow(w->lab, (size_t)B)))
         return rc;
-    if (w->lab) (void)hipFree(w->lab);
-    w->lab = nullptr;
-    TR_TRY(hipMalloc(&w->lab, (size_t)B * sizeof(int32_t)));
     w->cap_B = B;
     return DG_OK;
 }
 
 // slots for this B (the same B always gives the same slots: the sums' order depends on B alone) and room for both halves
-int plan_slots(TrainWork* w, const Plan& p, int B) {
+int plan_slots(const dg_clf* h, TrainWork* w, const Plan& p, int B) {
     for (int j : p.params) {
-        const WGeo q = geometry(p.L[j], B);
+        const WGeo q = geometry(h->layers[j], B);
         int S = 0, Kc = 0;
         slot_plan(q, &S, &Kc);
-        const size_t need = 2 * (size_t)S * (q.M + 1) * q.N;
-        if (need > w->part_floats[j]) {
-            int rc = grow(w->part[j], need);
-            if (rc) return rc;
-            w->part_floats[j] = need;
-        }
+        int rc = clf_grow(&w->part[j], 1, w->part_floats[j], 2 * (size_t)S * (q.M + 1) * q.N);
+        if (rc) return rc;
         w->slots[j] = S;
         w->kc[j] = Kc;
     }
@@ -403,13 +351,13 @@ void launch_dropout(const float* x, float* y, float* mask, long long total, floa
 void forward_pass(dg_clf* h, TrainWork* w, const Plan& p, const float* x, int B, int pass, uint64_t seed, int64_t step, hipStream_t s) {
     const float* cur = x;
     for (int j = 0; j <= p.last; ++j) {
-        const DgClfLayerView& v = p.L[j];
+        const ClfLayer& v = h->layers[j];
         if (!has_output(v)) continue;
         w->in[j] = cur;
         if (v.kind == DG_LAYER_DROPOUT)
-            launch_dropout(cur, w->act[j], w->mask[j], (long long)B * features(v), v.keep_prob, seed, j, pass, step, s);
+            launch_dropout(cur, w->act[j], w->mask[j], (long long)B * v.features(), v.keep_prob, seed, j, pass, step, s);
         else
-            dg_clf_launch_forward(h, j, cur, w->act[j], B, s);
+            clf_launch_forward(h, j, cur, w->act[j], B, s);
         cur = w->act[j];
     }
 }
@@ -419,24 +367,24 @@ const float* backward_pass(dg_clf* h, TrainWork* w, const Plan& p, const float* 
     const float* g = seed;
     int which = 0;
     for (int j = p.last; j >= 0; --j) {
-        const DgClfLayerView& v = p.L[j];
+        const ClfLayer& v = h->layers[j];
         if (!has_output(v)) continue;
-        if (half >= 0 && has_params(v)) {
+        if (half >= 0 && v.has_params()) {
             WGeo q = geometry(v, B);
             q.Kc = w->kc[j];
             const int S = w->slots[j];
             float* part = w->part[j] + (size_t)half * S * (q.M + 1) * q.N;
             hipLaunchKernelGGL(tr_wgrad_kernel, dim3((unsigned)((q.M + 1 + WT - 1) / WT), (unsigned)((q.N + WT - 1) / WT), (unsigned)S),
-                               dim3(256), 0, s, w->in[j], g, w->act[j], v.fused_relu, part, q);
+                               dim3(256), 0, s, w->in[j], g, w->act[j], v.fused_relu ? 1 : 0, part, q);
         }
         if (!to_input && j <= p.first_param) break;              // nothing below needs a gradient
         float* dx = w->gbuf[which ^ 1];
         if (v.kind == DG_LAYER_DROPOUT) {
-            const long long total = (long long)B * features(v);
+            const long long total = (long long)B * v.features();
             hipLaunchKernelGGL(tr_dropout_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, w->mask[j], dx, total,
                                v.keep_prob);
         } else {
-            dg_clf_launch_input_grad(h, j, g, w->act[j], dx, B, s);
+            clf_launch_input_grad(h, j, g, w->act[j], dx, B, s);
         }
         which ^= 1;
         g = dx;
@@ -451,28 +399,28 @@ int gradient_step(dg_clf* h, TrainWork* w, const Plan& p, const float* x, const 
     const float scale = (adv ? 0.5f : 1.0f) / (float)B;
     const unsigned rgrid = (unsigned)((B + 63) / 64);
     forward_pass(h, w, p, x, B, 0, seed, step, s);
-    hipLaunchKernelGGL(tr_ce_kernel, dim3(rgrid), dim3(64), 0, s, w->act[p.last], lab, w->seed, w->ce, B, p.n, scale);
+    hipLaunchKernelGGL(tr_ce_kernel, dim3(rgrid), dim3(64), 0, s, w->act[p.last], lab, w->seed, w->ce, B, h->n_logits, scale);
     backward_pass(h, w, p, w->seed, B, 0, false, s);
     if (adv) {
         forward_pass(h, w, p, x, B, 1, seed, step, s);
-        dg_clf_launch_ce_grad(w->act[p.last], nullptr, w->seed, B, p.n, s);
+        clf_launch_ce_grad(w->act[p.last], nullptr, w->seed, B, h->n_logits, s);
         const float* gin = backward_pass(h, w, p, w->seed, B, -1, true, s);
-        dg_clf_launch_fgsm(x, gin, w->xadv, (long long)B * p.P, adv_eps, lo, hi, s);
+        clf_launch_fgsm(x, gin, w->xadv, (long long)B * h->pixels(), adv_eps, lo, hi, s);
         forward_pass(h, w, p, w->xadv, B, 2, seed, step, s);
-        hipLaunchKernelGGL(tr_ce_kernel, dim3(rgrid), dim3(64), 0, s, w->act[p.last], lab, w->seed, w->ce + B, B, p.n, scale);
+        hipLaunchKernelGGL(tr_ce_kernel, dim3(rgrid), dim3(64), 0, s, w->act[p.last], lab, w->seed, w->ce + B, B, h->n_logits, scale);
         backward_pass(h, w, p, w->seed, B, 1, false, s);
-        if (x_adv_out) TR_TRY(hipMemcpyAsync(x_adv_out, w->xadv, (size_t)B * p.P * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (x_adv_out) CLF_TRY(hipMemcpyAsync(x_adv_out, w->xadv, (size_t)B * h->pixels() * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     hipLaunchKernelGGL(tr_loss_kernel, dim3(1), dim3(64), 0, s, w->ce, B, adv ? 2 : 1, loss);
-    TR_TRY(hipGetLastError());
+    CLF_TRY(hipGetLastError());
     return DG_OK;
 }
 
 // the slot reduction of every parameter layer: gradients to grads (concatenated (W; b) per layer) and / or Adam with lr_t
-int reduce(TrainWork* w, const Plan& p, int B, bool adv, float* grads, bool adam, float lr_t, hipStream_t s) {
+int reduce(const dg_clf* h, TrainWork* w, const Plan& p, int B, bool adv, float* grads, bool adam, float lr_t, hipStream_t s) {
     size_t off = 0;
     for (int j : p.params) {
-        const DgClfLayerView& v = p.L[j];
+        const ClfLayer& v = h->layers[j];
         const WGeo q = geometry(v, B);
         const long long per = (long long)(q.M + 1) * q.N;
         hipLaunchKernelGGL(tr_reduce_adam_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s, w->part[j], w->slots[j] * (adv ? 2 : 1),
@@ -480,26 +428,23 @@ int reduce(TrainWork* w, const Plan& p, int B, bool adv, float* grads, bool adam
                            grads ? grads + off : nullptr, lr_t);
         off += (size_t)per;
     }
-    TR_TRY(hipGetLastError());
+    CLF_TRY(hipGetLastError());
     return DG_OK;
 }
 
-int prepare(dg_clf* h, Plan* p, TrainWork** out, int B) {
-    TrainWork** slot = nullptr;
-    int rc = plan_of(h, p, &slot);
+// the plan, and h->tr ready for batches of B images
+int prepare(dg_clf* h, Plan* p, int B) {
+    int rc = plan_of(h, p);
     if (rc) return rc;
-    TR_TRY(hipSetDevice(p->device));
-    if (!*slot) *slot = new TrainWork();
-    if ((rc = ensure(*slot, *p, B)) || (rc = plan_slots(*slot, *p, B))) return rc;
-    *out = *slot;
-    return DG_OK;
+    CLF_TRY(hipSetDevice(h->device));
+    if (!h->tr) h->tr = new TrainWork();
+    if ((rc = ensure(h, h->tr, *p, B))) return rc;
+    return plan_slots(h, h->tr, *p, B);
 }
 
 }  // namespace
 
-extern "C" {
-
-__attribute__((visibility("hidden"))) void dg_train_release(TrainWork* w) {
+void train_release(TrainWork* w) {
     if (!w) return;
     auto drop = [](auto& vec) {
         for (auto* q : vec)
@@ -512,86 +457,82 @@ __attribute__((visibility("hidden"))) void dg_train_release(TrainWork* w) {
     delete w;
 }
 
+extern "C" {
+
 int dg_clf_adam_reset(dg_clf* h) {
-    if (!h) return fail(DG_E_INVALID, "null handle");
+    if (!h) return clf_fail(DG_E_INVALID, "null handle");
     Plan p;
-    TrainWork* w = nullptr;
-    int rc = prepare(h, &p, &w, 1);
+    int rc = prepare(h, &p, 1);
     if (rc) return rc;
+    TrainWork* w = h->tr;
     for (int j : p.params) {
-        const WGeo q = geometry(p.L[j], 1);
-        const size_t per = (size_t)(q.M + 1) * q.N;
-        TR_TRY(hipMemset(w->m[j], 0, per * sizeof(float)));
-        TR_TRY(hipMemset(w->v[j], 0, per * sizeof(float)));
+        const size_t per = param_floats(h->layers[j]);
+        CLF_TRY(hipMemset(w->m[j], 0, per * sizeof(float)));
+        CLF_TRY(hipMemset(w->v[j], 0, per * sizeof(float)));
     }
     w->t = 0;
     return DG_OK;
 }
 
 int dg_clf_get_adam(dg_clf* h, int layer, float* m, float* v, int64_t* t, int is_device) {
-    if (!h) return fail(DG_E_INVALID, "null handle");
+    if (!h) return clf_fail(DG_E_INVALID, "null handle");
     Plan p;
-    TrainWork* w = nullptr;
-    int rc = prepare(h, &p, &w, 1);
+    int rc = prepare(h, &p, 1);
     if (rc) return rc;
-    if (layer < 0 || layer >= (int)p.L.size() || !has_params(p.L[layer])) return fail(DG_E_INVALID, "layer %d has no parameters", layer);
-    const WGeo q = geometry(p.L[layer], 1);
-    const size_t per = (size_t)(q.M + 1) * q.N;
+    TrainWork* w = h->tr;
+    if (layer < 0 || layer >= (int)h->layers.size() || !h->layers[layer].has_params())
+        return clf_fail(DG_E_INVALID, "layer %d has no parameters", layer);
+    const size_t per = param_floats(h->layers[layer]);
     const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (m) TR_TRY(hipMemcpy(m, w->m[layer], per * sizeof(float), kind));
-    if (v) TR_TRY(hipMemcpy(v, w->v[layer], per * sizeof(float), kind));
+    if (m) CLF_TRY(hipMemcpy(m, w->m[layer], per * sizeof(float), kind));
+    if (v) CLF_TRY(hipMemcpy(v, w->v[layer], per * sizeof(float), kind));
     if (t) *t = w->t;
     return DG_OK;
 }
 
 int dg_clf_dropout_mask(dg_clf* h, int layer, int B, uint64_t seed, int64_t step, int pass, float* mask, void* stream) {
-    if (!h || !mask || B <= 0) return fail(DG_E_INVALID, "dg_clf_dropout_mask: bad argument");
-    if (layer < 0 || layer >= dg_clf_layer_count(h)) return fail(DG_E_INVALID, "layer %d out of range", layer);
-    DgClfLayerView v;
-    dg_clf_layer_view(h, layer, &v);
-    if (v.kind != DG_LAYER_DROPOUT || !(v.keep_prob > 0.f)) return fail(DG_E_INVALID, "layer %d is not a Dropout layer with a keep_prob", layer);
-    int device = 0, P = 0, hw = 0;
-    dg_clf_train_slot(h, &device, &P, &hw);
-    TR_TRY(hipSetDevice(device));
-    launch_dropout(nullptr, nullptr, mask, (long long)B * features(v), v.keep_prob, seed, layer, pass, step, (hipStream_t)stream);
-    TR_TRY(hipGetLastError());
+    if (!h || !mask || B <= 0) return clf_fail(DG_E_INVALID, "dg_clf_dropout_mask: bad argument");
+    if (layer < 0 || layer >= (int)h->layers.size()) return clf_fail(DG_E_INVALID, "layer %d out of range", layer);
+    const ClfLayer& v = h->layers[layer];
+    if (v.kind != DG_LAYER_DROPOUT || !(v.keep_prob > 0.f)) return clf_fail(DG_E_INVALID, "layer %d is not a Dropout layer with a keep_prob", layer);
+    CLF_TRY(hipSetDevice(h->device));
+    launch_dropout(nullptr, nullptr, mask, (long long)B * v.features(), v.keep_prob, seed, layer, pass, step, (hipStream_t)stream);
+    CLF_TRY(hipGetLastError());
     return DG_OK;
 }
 
 int dg_clf_param_gradient(dg_clf* h, const float* x, const int32_t* labels, int B, float adv_eps, float clip_min, float clip_max,
                           uint64_t seed, int64_t step, float* grads, float* loss, float* x_adv, void* stream) {
-    if (!h || !x || !labels || !grads || B <= 0) return fail(DG_E_INVALID, "dg_clf_param_gradient: bad argument");
-    if (adv_eps > 0.f && !(clip_max > clip_min)) return fail(DG_E_INVALID, "dg_clf_param_gradient: clip [%g, %g] is empty", (double)clip_min, (double)clip_max);
+    if (!h || !x || !labels || !grads || B <= 0) return clf_fail(DG_E_INVALID, "dg_clf_param_gradient: bad argument");
+    if (adv_eps > 0.f && !(clip_max > clip_min)) return clf_fail(DG_E_INVALID, "dg_clf_param_gradient: clip [%g, %g] is empty", (double)clip_min, (double)clip_max);
     Plan p;
-    TrainWork* w = nullptr;
-    int rc = prepare(h, &p, &w, B);
+    int rc = prepare(h, &p, B);
     if (rc) return rc;
+    TrainWork* w = h->tr;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = gradient_step(h, w, p, x, labels, B, adv_eps, clip_min, clip_max, seed, step, loss ? loss : w->loss, x_adv, s))) return rc;
-    return reduce(w, p, B, adv_eps > 0.f, grads, false, 0.f, s);
+    return reduce(h, w, p, B, adv_eps > 0.f, grads, false, 0.f, s);
 }
 
 int dg_clf_train(dg_clf* h, const float* X, const int32_t* labels, int n, const int32_t* idx, int n_steps, int batch_size,
                  float learning_rate, float adv_eps, float clip_min, float clip_max, uint64_t seed, float* losses, void* stream) {
-    if (!h || !X || !labels || !idx || n <= 0 || n_steps < 0 || batch_size <= 0) return fail(DG_E_INVALID, "dg_clf_train: bad argument");
-    if (adv_eps > 0.f && !(clip_max > clip_min)) return fail(DG_E_INVALID, "dg_clf_train: clip [%g, %g] is empty", (double)clip_min, (double)clip_max);
+    if (!h || !X || !labels || !idx || n <= 0 || n_steps < 0 || batch_size <= 0) return clf_fail(DG_E_INVALID, "dg_clf_train: bad argument");
+    if (adv_eps > 0.f && !(clip_max > clip_min)) return clf_fail(DG_E_INVALID, "dg_clf_train: clip [%g, %g] is empty", (double)clip_min, (double)clip_max);
     Plan p;
-    TrainWork* w = nullptr;
-    int rc = prepare(h, &p, &w, batch_size);
+    int rc = prepare(h, &p, batch_size);
     if (rc) return rc;
+    TrainWork* w = h->tr;
     hipStream_t s = (hipStream_t)stream;
-    const long long total = (long long)batch_size * p.P;
+    const long long P = h->pixels(), total = batch_size * P;
     const bool adv = adv_eps > 0.f;
     for (int st = 0; st < n_steps; ++st) {
         hipLaunchKernelGGL(tr_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, X, labels, idx + (long long)st * batch_size, n,
-                           (long long)p.P, batch_size, w->xb, w->lab);
+                           P, batch_size, w->xb, w->lab);
         if ((rc = gradient_step(h, w, p, w->xb, w->lab, batch_size, adv_eps, clip_min, clip_max, seed, w->t, losses ? losses + st : w->loss,
                                 nullptr, s)))
             return rc;
         w->t += 1;
-        const double t = (double)w->t;
-        const float lr_t = (float)((double)learning_rate * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.9, t)));
-        if ((rc = reduce(w, p, batch_size, adv, nullptr, true, lr_t, s))) return rc;
+        if ((rc = reduce(h, w, p, batch_size, adv, nullptr, true, dg_tf_adam_lr(learning_rate, (double)w->t), s))) return rc;
     }
     return DG_OK;
 }

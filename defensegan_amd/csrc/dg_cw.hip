@@ -43,43 +43,17 @@
 // keep running over all N images.  tools/cw_time.py measures abort_early on and off.  gfx950 only.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 
-#include "../../include/defensegan_hip.h"
-
-struct CwWork;
-extern "C" {
-__attribute__((visibility("hidden"))) void dg_set_error_message(const char* msg);    // dg_engine.cpp
-__attribute__((visibility("hidden"))) int dg_clf_kept_forward(dg_clf* h, const float* x, int B, hipStream_t s, const float** logits);
-__attribute__((visibility("hidden"))) int dg_clf_seeded_backward(dg_clf* h, const float* seed, int B, hipStream_t s, float** grad);
-__attribute__((visibility("hidden"))) CwWork** dg_clf_cw_slot(dg_clf* h, int* device, int* P, int* n);
-}
+#include "dg_clf_internal.h"
+#include "dg_shared_math.h"
 
 struct CwWork {
-    void* mem = nullptr;
+    char* mem = nullptr;
     size_t bytes = 0;
 };
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    dg_set_error_message(buf);
-    return code;
-}
-
-#define CW_TRY(expr)                                                                                \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return fail(DG_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
 
 // the workspace, carved from one allocation: N x P planes, the seed, per-image and per-chunk scalars
 struct CwBufs {
@@ -307,9 +281,8 @@ __global__ __launch_bounds__(256) void cw_update_kernel(CwBufs bf, const float* 
     const float w = bf.w[i];
     const float th = tanhf(w + ti);
     const float g = (grad[i] + 2.0f * (ni - bf.other[i])) * ((hi - lo) * 0.5f * (1.0f - th * th));
-    const float m = 0.9f * bf.m[i] + 0.1f * g;
-    const float v = 0.999f * bf.v[i] + 0.001f * (g * g);
-    const float wn = w - lr_t * m / (sqrtf(v) + 1e-8f);
+    float m = bf.m[i], v = bf.v[i];
+    const float wn = w - dg_tf_adam_step(m, v, g, lr_t);
     bf.m[i] = m;
     bf.v[i] = v;
     bf.w[i] = wn;
@@ -318,47 +291,38 @@ __global__ __launch_bounds__(256) void cw_update_kernel(CwBufs bf, const float* 
 
 }  // namespace
 
-extern "C" {
-
-__attribute__((visibility("hidden"))) void dg_cw_release(CwWork* w) {
+void cw_release(CwWork* w) {
     if (!w) return;
     if (w->mem) (void)hipFree(w->mem);
     delete w;
 }
 
+extern "C" {
+
 int dg_cw(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted, int batch_size, float confidence, float learning_rate,
           int binary_search_steps, int max_iterations, int abort_early, double initial_const, float clip_min, float clip_max,
           float* x_adv, float* best_l2, int32_t* best_class, double* final_const, int32_t* chunk_stop, void* stream) {
-    if (!h || !x || !x_adv || B <= 0) return fail(DG_E_INVALID, "dg_cw: bad argument");
+    if (!h || !x || !x_adv || B <= 0) return clf_fail(DG_E_INVALID, "dg_cw: bad argument");
     if (batch_size <= 0 || binary_search_steps < 0 || max_iterations < 0 || !(clip_max > clip_min))
-        return fail(DG_E_INVALID, "dg_cw: bad parameters (batch_size %d, binary_search_steps %d, max_iterations %d, clip [%g, %g])",
-                    batch_size, binary_search_steps, max_iterations, (double)clip_min, (double)clip_max);
-    int device = 0, Pi = 0, n = 0;
-    CwWork** slot = dg_clf_cw_slot(h, &device, &Pi, &n);
-    if (n <= 0) return fail(DG_E_STATE, "dg_cw: classifier has no layers");
-    CW_TRY(hipSetDevice(device));
+        return clf_fail(DG_E_INVALID, "dg_cw: bad parameters (batch_size %d, binary_search_steps %d, max_iterations %d, clip [%g, %g])",
+                        batch_size, binary_search_steps, max_iterations, (double)clip_min, (double)clip_max);
+    const int n = h->n_logits;
+    if (n <= 0) return clf_fail(DG_E_STATE, "dg_cw: classifier has no layers");
+    CLF_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const long long N = B, P = Pi, chunks = (N + batch_size - 1) / batch_size;
+    const long long N = B, P = h->pixels(), chunks = (N + batch_size - 1) / batch_size;
     CwBufs bf;
     const size_t need = carve(&bf, nullptr, N, P, n, chunks);
-    if (!*slot) *slot = new CwWork();
-    CwWork* wk = *slot;
-    if (need > wk->bytes) {
-        if (wk->mem) (void)hipFree(wk->mem);
-        wk->mem = nullptr;
-        wk->bytes = 0;
-        CW_TRY(hipMalloc(&wk->mem, need));
-        wk->bytes = need;
-    }
-    carve(&bf, (char*)wk->mem, N, P, n, chunks);
+    if (!h->cw) h->cw = new CwWork();
+    int rc = clf_grow(&h->cw->mem, 1, h->cw->bytes, need);
+    if (rc) return rc;
+    carve(&bf, h->cw->mem, N, P, n, chunks);
 
     const float lo = clip_min, hi = clip_max;
-    const float* logits = nullptr;
-    int rc = DG_OK;
-    if (!labels && (rc = dg_clf_kept_forward(h, x, B, s, &logits))) return rc;      // the model's own prediction on x
-    hipLaunchKernelGGL(cw_setup_kernel, dim3((unsigned)N), dim3(256), 0, s, x, labels, labels ? nullptr : logits, n, P, lo, hi,
-                       initial_const, bf, x_adv);
-    CW_TRY(hipGetLastError());
+    if (!labels && (rc = clf_kept_forward(h, x, B, s))) return rc;      // the model's own prediction on x
+    hipLaunchKernelGGL(cw_setup_kernel, dim3((unsigned)N), dim3(256), 0, s, x, labels, labels ? nullptr : h->acts[h->logit_layer], n, P,
+                       lo, hi, initial_const, bf, x_adv);
+    CLF_TRY(hipGetLastError());
     const long long total = N * P;
     const unsigned egrid = (unsigned)((total + 255) / 256);
     const int every = max_iterations / 10 > 0 ? max_iterations / 10 : 1;
@@ -367,28 +331,28 @@ int dg_cw(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted,
         hipLaunchKernelGGL(cw_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, P, batch_size, step > 0 ? 1 : 0, 1, repeat_last,
                            targeted ? 1 : 0, lo, hi);
         for (int it = 0; it < max_iterations; ++it) {
-            if ((rc = dg_clf_kept_forward(h, bf.newimg, B, s, &logits))) return rc;
-            hipLaunchKernelGGL(cw_head_kernel, dim3((unsigned)N), dim3(256), 0, s, logits, n, P, batch_size, targeted ? 1 : 0, confidence, bf);
+            if ((rc = clf_kept_forward(h, bf.newimg, B, s))) return rc;
+            hipLaunchKernelGGL(cw_head_kernel, dim3((unsigned)N), dim3(256), 0, s, h->acts[h->logit_layer], n, P, batch_size, targeted ? 1 : 0,
+                               confidence, bf);
             float* grad = nullptr;
-            if ((rc = dg_clf_seeded_backward(h, bf.seed, B, s, &grad))) return rc;
+            if ((rc = clf_seeded_backward(h, bf.seed, B, s, &grad))) return rc;
             hipLaunchKernelGGL(cw_chunk_kernel, dim3((unsigned)chunks), dim3(256), 0, s, bf, B, batch_size, it,
                                (abort_early && it % every == 0) ? 1 : 0);
-            const double t = it + 1;
-            const float lr_t = (float)((double)learning_rate * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.9, t)));
-            hipLaunchKernelGGL(cw_update_kernel, dim3(egrid), dim3(256), 0, s, bf, grad, x_adv, total, P, batch_size, it, lr_t, lo, hi);
-            CW_TRY(hipGetLastError());
+            hipLaunchKernelGGL(cw_update_kernel, dim3(egrid), dim3(256), 0, s, bf, grad, x_adv, total, P, batch_size, it,
+                               dg_tf_adam_lr(learning_rate, it + 1), lo, hi);
+            CLF_TRY(hipGetLastError());
         }
         if (chunk_stop)
-            CW_TRY(hipMemcpyAsync(chunk_stop + (long long)step * chunks, bf.abort_iter, chunks * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            CLF_TRY(hipMemcpyAsync(chunk_stop + (long long)step * chunks, bf.abort_iter, chunks * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     }
     if (final_const) {
         if (binary_search_steps > 0)
             hipLaunchKernelGGL(cw_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, P, batch_size, 1, 0, 0, targeted ? 1 : 0, lo, hi);
-        CW_TRY(hipGetLastError());
-        CW_TRY(hipMemcpyAsync(final_const, bf.cst, N * sizeof(double), hipMemcpyDeviceToDevice, s));
+        CLF_TRY(hipGetLastError());
+        CLF_TRY(hipMemcpyAsync(final_const, bf.cst, N * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
-    if (best_l2) CW_TRY(hipMemcpyAsync(best_l2, bf.obestl2, N * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (best_class) CW_TRY(hipMemcpyAsync(best_class, bf.obestscore, N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (best_l2) CLF_TRY(hipMemcpyAsync(best_l2, bf.obestl2, N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (best_class) CLF_TRY(hipMemcpyAsync(best_class, bf.obestscore, N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return DG_OK;
 }
 

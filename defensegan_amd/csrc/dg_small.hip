@@ -1,5 +1,6 @@
 // Small kernels of the projection loop (gfx950): momentum update, restart selection, latent init.
 #include "dg_kernels.h"
+#include "dg_shared_math.h"
 
 namespace dg {
 
@@ -98,16 +99,6 @@ void launch_select(const float* loss, const float* y, int B, int R, int P, float
 // ---- latent init: z ~ N(0, std^2), Philox4x32-10 + Box-Muller ------------------------------------
 // counter = (global row lo, global row hi, column/4, 0), key = (seed lo, seed hi): the draw of a row
 // depends only on (seed, global row), never on batching or on the GPU count.
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
 __global__ __launch_bounds__(256) void init_latents_kernel(float* __restrict__ z, long long n_rows, int latent,
                                                            unsigned long long seed, long long first_row,
                                                            float std) {
@@ -118,10 +109,12 @@ __global__ __launch_bounds__(256) void init_latents_kernel(float* __restrict__ z
     const int cq = (int)(i - row * q);
     const unsigned long long grow = (unsigned long long)(first_row + row);
     uint32_t c[4] = {(uint32_t)grow, (uint32_t)(grow >> 32), (uint32_t)cq, 0u};
+    // dg_philox4x32_10's loop, kept here: called as that function the compiler orders the operands of three XORs of this kernel
+    // the other way round (same values, other instruction bytes), and this kernel's code is held fixed
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
+        dg_philox_round(c, k0, k1);
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
     }
