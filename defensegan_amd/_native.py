@@ -61,6 +61,9 @@ SYMBOLS = [
     ("dg_clf_dropout_mask", _i, [_vp, _i, _i, _u64, _i64, _i, _vp, _vp]),
     ("dg_clf_param_gradient", _i, [_vp, _vp, _vp, _i, _f, _f, _f, _u64, _i64, _vp, _vp, _vp, _vp]),
     ("dg_clf_train", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _f, _u64, _vp, _vp]),
+    ("dg_clf_class_gradient", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    ("dg_clf_jacobian", _i, [_vp, _vp, _i, _i, _vp, _vp]),
+    ("dg_jacobian_augment", _i, [_vp, _vp, _vp, _i, _f, _i, _vp, _vp]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

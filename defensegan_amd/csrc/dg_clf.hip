@@ -365,6 +365,7 @@ int dg_clf_destroy(dg_clf* h) {
         if (p) (void)hipFree(p);
     cw_release(h->cw);
     train_release(h->tr);
+    jac_release(h->jac);
     delete h;
     return DG_OK;
 }

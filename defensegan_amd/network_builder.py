@@ -446,6 +446,79 @@ def _mlp_backward(self, x, dlogits):
 MLP.backward = _mlp_backward
 
 
+_JAC_REC_NOTE = (
+    "class_gradient / jacobian on a model with the Defense-GAN reconstruction layer attached (add_rec_model) is not implemented: "
+    "the reference takes the Jacobian of the SUBSTITUTE (blackbox.py:170-174), a bare classifier, and the gradient through "
+    "ReconstructionLayer is identically zero there (network_builder.py:266-271).  Differentiate the model before add_rec_model.")
+
+
+def _jacobian_input(self, x):
+    """(device tensor [B, H, W, C], was_numpy) for the class-gradient entries: the checks of ``backward``."""
+    import torch
+    if self.rec_layer is not None:
+        raise NotImplementedError(_JAC_REC_NOTE)
+    self._ensure()
+    if not self._weights_set:
+        raise _native.NativeError("classifier weights not set")
+    was_numpy = isinstance(x, np.ndarray)
+    dev = torch.device("cuda", self._device)
+    t = (torch.from_numpy(np.ascontiguousarray(x, np.float32)) if was_numpy else x).to(device=dev, dtype=torch.float32).contiguous()
+    if t.dim() != 4 or tuple(t.shape[1:]) != tuple(self.input_shape[1:]) or int(t.shape[0]) == 0:
+        raise ValueError("x must be [B, %s] with B > 0, got %s" % (", ".join(str(v) for v in self.input_shape[1:]), tuple(t.shape)))
+    return t, was_numpy
+
+
+def _class_indices(self, classes, B, what="classes"):
+    """int32 device tensor [B].  Class indices on the host are checked against [0, nb_classes); a device tensor is taken as it
+    is (an index outside the range gives a zero gradient there, as training's out-of-range label does)."""
+    import torch
+    dev = torch.device("cuda", self._device)
+    if not isinstance(classes, torch.Tensor):
+        c = np.asarray(classes)
+        if c.ndim == 0:
+            c = np.full(B, c)
+        if c.shape != (B,) or not (c == np.round(c)).all() or (c < 0).any() or (c >= self.nb_classes).any():
+            raise ValueError("%s must be %d class indices in [0, %d)" % (what, B, self.nb_classes))
+        classes = torch.from_numpy(np.ascontiguousarray(c.astype(np.int32)))
+    elif tuple(classes.shape) != (B,):
+        raise ValueError("%s must be [%d], got %s" % (what, B, tuple(classes.shape)))
+    return classes.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _mlp_class_gradient(self, x, classes, of_probs=True):
+    """d out(x)[b, classes[b]] / dx on the device (``dg_clf_class_gradient``): one row of cleverhans' ``jacobian_graph`` per image.
+    ``out`` is what ``model(x)`` returns -- the probabilities -- when ``of_probs`` and the model ends in Softmax, otherwise the
+    logits.  ``classes``: [B] class indices (or one index for every image).  NumPy in gives NumPy out, torch in gives torch out on
+    the caller's current stream.  Bare classifier only (NotImplementedError with the reconstruction layer attached)."""
+    import torch
+    t, was_numpy = _jacobian_input(self, x)
+    B = int(t.shape[0])
+    c = _class_indices(self, classes, B)
+    g = torch.empty_like(t)
+    stream = torch.cuda.current_stream(t.device).cuda_stream
+    with torch.cuda.device(t.device):
+        _native.check(_native.load().dg_clf_class_gradient(self._handle, t.data_ptr(), c.data_ptr(), B, 1 if of_probs else 0,
+                                                           g.data_ptr(), stream))
+    return g.cpu().numpy() if was_numpy else g
+
+
+def _mlp_jacobian(self, x, of_probs=True):
+    """[B, nb_classes, H, W, C]: d out(x)[b, k] / dx for every class (``dg_clf_jacobian``: one forward, nb_classes backwards) --
+    cleverhans' ``jacobian_graph`` evaluated at ``x``, list index k on axis 1.  Same conventions as ``class_gradient``."""
+    import torch
+    t, was_numpy = _jacobian_input(self, x)
+    B = int(t.shape[0])
+    jac = torch.empty((B, self.nb_classes) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device)
+    stream = torch.cuda.current_stream(t.device).cuda_stream
+    with torch.cuda.device(t.device):
+        _native.check(_native.load().dg_clf_jacobian(self._handle, t.data_ptr(), B, 1 if of_probs else 0, jac.data_ptr(), stream))
+    return jac.cpu().numpy() if was_numpy else jac
+
+
+MLP.class_gradient = _mlp_class_gradient
+MLP.jacobian = _mlp_jacobian
+
+
 class FastGradientMethod(object):
     """The cleverhans attack object the reference instantiates (whitebox.py:198-200, blackbox.py:530-534), ord = inf only:
     ``adv = clip(x + eps * sign(grad_x CE(model(x), y)), clip_min, clip_max)``; without ``y`` the model's own prediction is

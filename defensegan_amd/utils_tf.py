@@ -150,6 +150,31 @@ def model_train(model, X_train, Y_train, args=None, rng=None, adv_eps=None, adv_
     return True
 
 
+def batch_eval(fn, X, batch_size=128):
+    """cleverhans utils_tf.batch_eval for one input and one output (blackbox.py:205-207): ``fn`` over the consecutive batches
+    X[0:bs], X[bs:2bs], ...; the last one is partial (NOT shifted back as model_train's is).  ``fn`` maps a batch to an array or
+    device tensor with the batch on axis 0; the outputs are concatenated in order, as the kind ``fn`` returned."""
+    batch_size = int(batch_size)
+    if batch_size <= 0:
+        raise ValueError("batch_size must be positive, got %d" % batch_size)
+    n = len(X)
+    outs = [fn(X[start:start + batch_size]) for start in range(0, n, batch_size)]
+    if not outs:
+        raise ValueError("X holds no rows")
+    if isinstance(outs[0], np.ndarray):
+        return np.concatenate(outs, axis=0)
+    import torch
+    return torch.cat(outs, dim=0)
+
+
+def batch_eval_labels(fn, X, batch_size=128):
+    """``np.argmax(batch_eval(...), axis=1)`` (blackbox.py:211): the labels an adversary reads off an oracle, NumPy int64 [n]."""
+    out = batch_eval(fn, X, batch_size)
+    if isinstance(out, np.ndarray):
+        return np.argmax(out, axis=1).astype(np.int64)
+    return out.argmax(dim=1).cpu().numpy().astype(np.int64)
+
+
 def adam_state(model, layer_nb):
     """(m, v, t) of the ``layer_nb``-th Conv2D / Linear layer: each moment as the (W, b) pair of its parameters."""
     model._ensure()

@@ -353,6 +353,25 @@ int dg_clf_train(dg_clf* h, const float* X, const int32_t* labels, int n, const 
                  float learning_rate, float adv_eps, float clip_min, float clip_max, uint64_t seed, float* losses, void* stream);
 
 /*
+ * The Jacobian side of the black-box substitute attack (/root/reference/blackbox.py:143-213: cleverhans' jacobian_graph and
+ * jacobian_augmentation, restated in defensegan_amd/csrc/dg_jacobian.hip's header comment and DESIGN.md section 7).  The reference
+ * differentiates model_sub(x), the PROBABILITIES: with of_probs != 0 on a model that ends in Softmax, out = softmax(logits) and the
+ * seed on the logits is TF's (delta_kc - p_c) * p_k; otherwise out = the logits and the seed is onehot(c).  Device pointers;
+ * asynchronous on `stream`, no host synchronisation, no float atomics: a call repeated returns the same bits.
+ */
+/* grad [B,in_h,in_w,in_c] = d out(x)[b, classes[b]] / dx; classes [B] int32.  A class outside [0, n) gives a zero gradient (the
+ * policy of training's out-of-range label), never a read outside the row. */
+int dg_clf_class_gradient(dg_clf* h, const float* x, const int32_t* classes, int B, int of_probs, float* grad, void* stream);
+/* jac [B, n, in_h, in_w, in_c]: one forward, n backwards; jac[:, k] has the bits of dg_clf_class_gradient with classes == k. */
+int dg_clf_jacobian(dg_clf* h, const float* x, int B, int of_probs, float* jac, void* stream);
+/* jacobian_augmentation: X [n,...], labels [n] int32 -> X_out [2n,...]: X_out[:n] = X (not copied when X_out == X, a buffer with
+ * room for 2n images), X_out[n + i] = X[i] + lmbda * sign(d softmax(logits(X[i]))[labels[i]] / dx), sign(0) = 0, NOT clipped.
+ * The new half is produced in chunks of batch_size images (a trailing partial chunk is a chunk of its own) inside the one call;
+ * the result does not depend on batch_size.  Any other overlap of X_out with X is DG_E_INVALID. */
+int dg_jacobian_augment(dg_clf* h, const float* X, const int32_t* labels, int n, float lmbda, int batch_size, float* X_out,
+                        void* stream);
+
+/*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
  * (no collective on the data path) and ONE all_gather assembles the evaluation message -- per rank `count` int32 words, e.g.
  * [n | labels (cap) | preds (cap) | diffs (cap, float32 bits)] as defensegan_amd/gan_defense.py:model_eval_gan_sharded builds it
