@@ -64,6 +64,8 @@ SYMBOLS = [
     ("dg_clf_class_gradient", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     ("dg_clf_jacobian", _i, [_vp, _vp, _i, _i, _vp, _vp]),
     ("dg_jacobian_augment", _i, [_vp, _vp, _vp, _i, _f, _i, _vp, _vp]),
+    ("dg_bpda_step", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp]),
+    ("dg_bpda_track", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

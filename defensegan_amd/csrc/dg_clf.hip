@@ -366,6 +366,7 @@ int dg_clf_destroy(dg_clf* h) {
     cw_release(h->cw);
     train_release(h->tr);
     jac_release(h->jac);
+    bpda_release(h->bpda);
     delete h;
     return DG_OK;
 }

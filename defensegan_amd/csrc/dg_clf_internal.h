@@ -1,5 +1,5 @@
-// The classifier handle as its four source files see it: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
-// dg_cw.hip (the Carlini-Wagner attack), dg_clf_train.hip (training) and dg_jacobian.hip (class gradients, Jacobian augmentation).  Everything here is internal to the library: plain C++
+// The classifier handle as its five source files see it: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
+// dg_cw.hip (the Carlini-Wagner attack), dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation) and dg_bpda.hip (the BPDA/EOT step).  Everything here is internal to the library: plain C++
 // under hidden visibility, nothing of it is exported.
 #pragma once
 
@@ -35,6 +35,7 @@ struct ClfLayer {
 struct CwWork;       // dg_cw.hip
 struct TrainWork;    // dg_clf_train.hip
 struct JacWork;      // dg_jacobian.hip
+struct BpdaWork;     // dg_bpda.hip
 
 struct dg_clf {
     int device = 0;
@@ -58,6 +59,7 @@ struct dg_clf {
     CwWork* cw = nullptr;                     // Carlini-Wagner workspace, grown on demand
     TrainWork* tr = nullptr;                  // training workspace and Adam state
     JacWork* jac = nullptr;                   // class-gradient seed, grown on demand
+    BpdaWork* bpda = nullptr;                 // BPDA's cross-entropy seed, grown on demand
 
     int pixels() const { return in_h * in_w * in_c; }
 };
@@ -104,5 +106,6 @@ int clf_seeded_backward(dg_clf* h, const float* seed, int B, hipStream_t s, floa
 void cw_release(CwWork* w);          // dg_cw.hip
 void train_release(TrainWork* w);    // dg_clf_train.hip
 void jac_release(JacWork* w);        // dg_jacobian.hip
+void bpda_release(BpdaWork* w);      // dg_bpda.hip
 
 #pragma GCC visibility pop

@@ -387,7 +387,8 @@ _REC_GRADIENT_NOTE = (
     "THROUGH ReconstructionLayer (whitebox.py:185-214, network_builder.py:266-271), whose gradient w.r.t. its input is "
     "identically zero (the projected latents live in variables updated by ApplyMomentum; the selected restart comes "
     "from an argmin) -- the input gradient is 0 and FGSM returns clip(x).  Build the attack before add_rec_model (or "
-    "pass no_rec=True) to differentiate the bare classifier.")
+    "pass no_rec=True) to differentiate the bare classifier.  For a white-box attack that uses the defense, see BPDA "
+    "(the real projection forward, the identity backward, averaged over its random restarts).")
 
 
 def _mlp_input_gradient(self, x, labels=None, no_rec=False):
@@ -566,7 +567,7 @@ _CW_REC_NOTE = (
     "reference the gradient through ReconstructionLayer is identically zero (network_builder.py:266-271), so the attack "
     "there reduces to repeated defended evaluations of the tanh round trip of x, whose per-iteration latent draws cannot be "
     "pinned.  Build the attack before add_rec_model, or on a model without it (no_rec), as bench.py's --strong flow does for "
-    "FGSM.")
+    "FGSM.  The white-box attack that does use the defense is BPDA (L-infinity, projected sign gradient).")
 
 
 class CarliniWagnerL2(object):
@@ -649,6 +650,201 @@ class CarliniWagnerL2(object):
         if not return_info:
             return res[0]
         return res if return_search else res[:3]
+
+
+# ---------------------------------------------------------------------- the attack that sees the defense: BPDA / EOT
+BPDA_NOISE_TAG = 0x42504441          # "BPDA": word 3 of the rand_init counter (the latents' draw has 0 there, dg_small.hip)
+BPDA_DEFAULT_SEED = 11241990         # model_eval_gan's default: without ``seed`` iteration 0 sees the evaluation's own latents
+
+
+def _philox4x32_10(ctr, key):
+    """Random123's Philox4x32-10 on the host: ctr [N, 4] uint32 values, key (k0, k1) -> [N, 4] uint64 arrays holding uint32
+    words.  The generator of the latent init and of Dropout (csrc/dg_shared_math.h), restated for the one draw made on the host."""
+    M = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(ctr[:, i], np.uint64) & M for i in range(4)]
+    k0, k1 = np.uint64(int(key[0]) & 0xFFFFFFFF), np.uint64(int(key[1]) & 0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & M, p1 & M, ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & M, p0 & M]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
+    return np.stack(c, axis=1)
+
+
+def bpda_rand_noise(n_images: int, row_elems: int, eps: float, seed: int, first_image: int = 0) -> np.ndarray:
+    """The ``rand_init`` draw of BPDA, float32 [n_images, row_elems] in [-eps, eps): element e of the image with GLOBAL index
+    i = first_image + row takes word e % 4 of Philox4x32-10(key = (seed lo, seed hi), counter = (e // 4, i lo, i hi,
+    BPDA_NOISE_TAG)); u = (word >> 8) * 2^-24 in [0, 1); noise = float32(eps) * (2 u - 1), one float32 rounding (2 u - 1 is exact).
+    Keyed by the image, so the draw does not depend on how the images are batched.  Drawn once per attack, on the host."""
+    n_images, row_elems, seed = int(n_images), int(row_elems), int(seed) & 0xFFFFFFFFFFFFFFFF
+    nq = (row_elems + 3) // 4
+    img = (np.arange(n_images, dtype=np.uint64) + np.uint64(int(first_image)))[:, None]
+    ctr = np.empty((n_images, nq, 4), np.uint64)
+    ctr[:, :, 0] = np.arange(nq, dtype=np.uint64)[None, :]
+    ctr[:, :, 1] = img & np.uint64(0xFFFFFFFF)
+    ctr[:, :, 2] = img >> np.uint64(32)
+    ctr[:, :, 3] = BPDA_NOISE_TAG
+    words = _philox4x32_10(ctr.reshape(-1, 4), (seed & 0xFFFFFFFF, seed >> 32)).reshape(n_images, nq * 4)[:, :row_elems]
+    u = (words >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return (np.float32(eps) * (np.float32(2.0) * u - np.float32(1.0))).astype(np.float32)
+
+
+def bpda_seed_schedule(seed: int, nb_iter: int, eot_samples: int):
+    """``(per_iteration, final)``: ``per_iteration[k][s] = seed + k * eot_samples + s`` is the latent seed of EOT sample s of
+    iteration k, ``final = seed + nb_iter * eot_samples`` that of the projection that judges the last iterate."""
+    m = int(eot_samples)
+    return [[int(seed) + k * m + s for s in range(m)] for k in range(int(nb_iter))], int(seed) + int(nb_iter) * m
+
+
+class BpdaDeviceOps(object):
+    """The four device operations ``BPDA.generate`` is made of, on tensors of the classifier's device and torch's current stream;
+    none of them waits for the device.  (``BPDA`` takes any object with these methods and a ``device``: the tests drive the loop
+    with a recording stand-in.)"""
+
+    def __init__(self, model: MLP):
+        import torch
+        model._ensure()
+        if not model._weights_set:
+            raise _native.NativeError("classifier weights not set")
+        self.model, self.gan = model, (model.rec_layer.rec_model if model.rec_layer is not None else None)
+        self.device = torch.device("cuda", model._device)
+
+    def project(self, x, seed, first_row):
+        """gan.reconstruct: latents drawn as dg_init_latents does for (seed, first_row + row)."""
+        return self.gan.reconstruct(x, seed=int(seed), first_row=int(first_row))
+
+    def predict(self, rec):
+        """[B] int32: the classifier's first argmax on ``rec`` (dg_eval_batch)."""
+        return self.model.eval_batch(rec, None, None, sync=False)[1]
+
+    def step(self, rec, labels, x_cur, x_orig, gsum, accumulate_only, eps, eps_iter, clip_min, clip_max, x_next):
+        """dg_bpda_step: the classifier's input gradient at ``rec``, then ``gsum += g`` (accumulate_only) or the projected sign
+        step of ``gsum + g`` from ``x_cur`` around ``x_orig`` into ``x_next``."""
+        import torch
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().dg_bpda_step(
+                self.model._handle, rec.data_ptr(), labels.data_ptr(), int(rec.shape[0]), ptr(x_cur), ptr(x_orig), ptr(gsum),
+                1 if accumulate_only else 0, float(eps), float(eps_iter), float(clip_min), float(clip_max), ptr(x_next),
+                torch.cuda.current_stream(self.device).cuda_stream))
+
+    def track(self, preds, labels, k, x_iter, x_best, first_success):
+        """dg_bpda_track: images still without a success take iterate k as their best, and k as their first success where
+        ``preds != labels``."""
+        import torch
+        B = int(preds.shape[0])
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().dg_bpda_track(
+                preds.data_ptr(), labels.data_ptr(), B, int(k), x_iter.data_ptr(), x_best.data_ptr(), first_success.data_ptr(),
+                int(x_iter.numel() // B), torch.cuda.current_stream(self.device).cuda_stream))
+
+
+class BPDA(object):
+    """The white-box attack that uses the defense: BPDA with EOT (Athalye, Carlini, Wagner 2018), L-infinity, on a model with
+    the Defense-GAN projection attached (``add_rec_model``).  Not in the reference, whose attacks differentiate through
+    ``ReconstructionLayer`` and see a zero gradient (_REC_GRADIENT_NOTE).  The projection runs for real in the forward pass and
+    counts as the identity in the backward pass; the gradient is summed over ``eot_samples`` projections with fresh latents:
+
+        x_0 = clip(x)            (``rand_init``: clip(x + bpda_rand_noise(...)); or ``x_init`` as given)
+        for k < nb_iter:   g_k = sum_{s < m} grad_r CE(logits(r), y) at r = reconstruct(x_k; latents of seed + k m + s)
+                           x_{k+1} = clip(x + clamp(x_k + eps_iter sign(g_k) - x, -eps, eps), clip_min, clip_max),  sign(0) = 0
+
+    Best tracking on the device: iterate k + 1 succeeds for an image when the defended prediction on it is not ``y``; that
+    prediction is read off the next iteration's first projection (s = 0), the last iterate's off one more projection with seed
+    ``seed + nb_iter m`` -- ``nb_iter * m + 1`` projections in all, enqueued with no host read in between.  ``generate`` returns
+    per image the first successful iterate, or the last iterate; ``return_info=True`` adds ``first_success`` [n] int32 (the
+    iterate's index in 1 .. nb_iter, or -1).
+
+    ``x`` NumPy or a device tensor [n, H, W, C] in generator range (NumPy in gives NumPy out; a tensor gives tensors on the
+    caller's current stream, not waited for); ``y`` class indices or one-hot rows, required.  ``seed`` defaults to
+    BPDA_DEFAULT_SEED.  The latents of image i are rows ``i * rec_rr + r`` of the seeded stream and every classifier output is
+    one thread's fixed-order sum, so the result does not depend on ``batch_size``, bit for bit: ``batch_size`` (default: the
+    reconstruction layer's) only bounds the images per engine call, and consecutive batches are coalesced into engine calls as
+    in ``gan_defense.model_eval_gan``.  With a USE_BN generator the rows of an engine call share its Batchnorm statistics: the
+    calls are then cut on ``batch_size`` exactly, and the result DOES depend on it.
+
+    A bare model raises ValueError: projected gradient descent on an undefended classifier is out of scope here.  A reconstruction
+    layer with a fixed ``z_init`` is refused as well (the attack draws fresh latents for every projection)."""
+
+    def __init__(self, model: MLP, back="tf", sess=None, ops=None):
+        self.model = model
+        self._ops = ops
+
+    def generate(self, x, y, eps=0.3, eps_iter=0.05, nb_iter=10, eot_samples=1, clip_min=None, clip_max=None, rand_init=False,
+                 seed=None, x_init=None, batch_size=None, return_info=False):
+        import torch
+        from . import gan_defense
+        m = self.model
+        rl = m.rec_layer
+        if rl is None:
+            raise ValueError("BPDA attacks a model with the Defense-GAN projection attached (add_rec_model); projected gradient "
+                             "descent on a bare classifier (PGD-on-bare) is out of scope")
+        if rl.z_init is not None:
+            raise ValueError("BPDA draws fresh latents for every projection; the reconstruction layer has a fixed z_init")
+        nb_iter, mm = int(nb_iter), int(eot_samples)
+        if nb_iter < 1:
+            raise ValueError("nb_iter must be >= 1, got %d" % nb_iter)
+        if mm < 1:
+            raise ValueError("eot_samples must be >= 1, got %d" % mm)
+        if not (float(eps) >= 0 and float(eps_iter) >= 0):
+            raise ValueError("eps and eps_iter must be >= 0")
+        if rand_init and x_init is not None:
+            raise ValueError("give rand_init or x_init, not both")
+        lo = float("-inf") if clip_min is None else float(clip_min)
+        hi = float("inf") if clip_max is None else float(clip_max)
+        if not lo <= hi:
+            raise ValueError("clip_min must not exceed clip_max")
+        seed = BPDA_DEFAULT_SEED if seed is None else int(seed)
+        ops = self._ops if self._ops is not None else BpdaDeviceOps(m)
+        dev = ops.device
+        was_numpy = isinstance(x, np.ndarray)
+        to = lambda a: (torch.from_numpy(np.ascontiguousarray(a, np.float32)) if isinstance(a, np.ndarray) else a).to(device=dev, dtype=torch.float32).contiguous()
+        t = to(x)
+        if t.dim() != 4 or tuple(t.shape[1:]) != tuple(m.input_shape[1:]) or int(t.shape[0]) == 0:
+            raise ValueError("x must be [n, %s] with n > 0, got %s" % (", ".join(str(d) for d in m.input_shape[1:]), tuple(t.shape)))
+        n, P = int(t.shape[0]), int(t[0].numel())
+        yy = np.asarray(y if isinstance(y, np.ndarray) else (y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y))
+        if yy.ndim > 1:
+            yy = yy.argmax(axis=-1)                                # one-hot labels as cleverhans takes them
+        if yy.shape != (n,):
+            raise ValueError("y must be %d class indices or one-hot rows" % n)
+        lab = torch.from_numpy(np.ascontiguousarray(yy.astype(np.int32))).to(dev)
+        if x_init is not None:
+            x_cur = to(x_init).clone()
+            if tuple(x_cur.shape) != tuple(t.shape):
+                raise ValueError("x_init must have x's shape")
+        elif rand_init:
+            noise = torch.from_numpy(bpda_rand_noise(n, P, eps, seed)).to(dev).view_as(t)
+            x_cur = torch.clamp(t + noise, lo, hi)
+        else:
+            x_cur = torch.clamp(t, lo, hi)
+        gan = rl.rec_model
+        R = int(gan.rec_rr)
+        bs = int(batch_size or rl.batch_size or n)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        step_n = gan_defense.engine_step(gan.reconstruct, bs, R, n)
+        cuts = [(a, min(n, a + step_n)) for a in range(0, n, step_n)]
+        x_next, x_best = torch.empty_like(x_cur), torch.empty_like(x_cur)
+        first_success = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        gsum = torch.empty_like(x_cur) if mm > 1 else None
+        seeds, final_seed = bpda_seed_schedule(seed, nb_iter, mm)
+        for k in range(nb_iter):
+            if gsum is not None:
+                gsum.zero_()
+            for s in range(mm):
+                for a, b in cuts:
+                    rec = ops.project(x_cur[a:b], seeds[k][s], a * R)
+                    if s == 0 and k > 0:                           # rec_{k,0} is the defended view of iterate k
+                        ops.track(ops.predict(rec), lab[a:b], k, x_cur[a:b], x_best[a:b], first_success[a:b])
+                    ops.step(rec, lab[a:b], x_cur[a:b], t[a:b], gsum[a:b] if gsum is not None else None, s < mm - 1, eps, eps_iter,
+                             lo, hi, x_next[a:b])
+            x_cur, x_next = x_next, x_cur
+        for a, b in cuts:
+            rec = ops.project(x_cur[a:b], final_seed, a * R)
+            ops.track(ops.predict(rec), lab[a:b], nb_iter, x_cur[a:b], x_best[a:b], first_success[a:b])
+        if was_numpy:
+            x_best, first_success = x_best.cpu().numpy(), first_success.cpu().numpy()
+        return (x_best, first_success) if return_info else x_best
 
 
 def rand_fgsm_prestep(test_images, eps: float, alpha: float, min_val: float = 0.0, max_val: float = 1.0, rng=None):

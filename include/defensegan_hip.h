@@ -372,6 +372,29 @@ int dg_jacobian_augment(dg_clf* h, const float* X, const int32_t* labels, int n,
                         void* stream);
 
 /*
+ * The white-box attack on the DEFENDED model (no reference counterpart: the reference's attacks differentiate through
+ * ReconstructionLayer, whose gradient is identically zero): BPDA with EOT, L-infinity -- the real projection forward, the identity
+ * as its backward, the gradient summed over the projection's random restarts, a projected sign step (defensegan_amd/csrc/dg_bpda.hip's
+ * header comment and DESIGN.md section 7 give the definition; network_builder.BPDA drives the two entries).  Device pointers;
+ * asynchronous on `stream`, no host synchronisation, no graph capture, no atomics.
+ */
+/* One (iteration, EOT sample): g = d CE(softmax(logits(rec)), labels) / d rec with the bits of dg_clf_input_gradient (labels [B]
+ * int32, required), then over the B x in_h x in_w x in_c elements either
+ *   accumulate_only != 0:  gsum += g                                   (gsum required; x_cur, x_orig, x_next unused, may be NULL)
+ *   accumulate_only == 0:  t = gsum + g (t = g when gsum == NULL; gsum is read, not written) and
+ *                          x_next = clip(x_orig + clamp(x_cur + eps_iter * sign(t) - x_orig, -eps, eps), clip_min, clip_max),
+ *                          sign(0) = 0; x_next is a buffer of its own.
+ * float4 loads and stores where in_h * in_w * in_c is a multiple of 4 and the pointers are 16-byte aligned. */
+int dg_bpda_step(dg_clf* h, const float* rec, const int32_t* labels, int B, const float* x_cur, const float* x_orig, float* gsum,
+                 int accumulate_only, float eps, float eps_iter, float clip_min, float clip_max, float* x_next, void* stream);
+/* Best tracking for iterate k (>= 0): for every image with first_success[b] < 0, x_best[b] = x_iter[b] (row_elems floats each),
+ * and first_success[b] = k where preds[b] != labels[b] as well.  An image that has succeeded is left alone, so x_best ends as the
+ * first misclassified iterate or the last iterate judged.  preds, labels, first_success [B] int32; x_best must not be x_iter.
+ * Runs on the current device. */
+int dg_bpda_track(const int32_t* preds, const int32_t* labels, int B, int k, const float* x_iter, float* x_best,
+                  int32_t* first_success, int64_t row_elems, void* stream);
+
+/*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
  * (no collective on the data path) and ONE all_gather assembles the evaluation message -- per rank `count` int32 words, e.g.
  * [n | labels (cap) | preds (cap) | diffs (cap, float32 bits)] as defensegan_amd/gan_defense.py:model_eval_gan_sharded builds it
