@@ -29,23 +29,58 @@ def test_same_padding_known_answers():
     assert CO.same_padding(5, 1, 3) == (2, 0, 0)
 
 
-@pytest.mark.parametrize("H,k,s,pad", [(28, 8, 2, "SAME"), (28, 5, 2, "SAME"), (14, 6, 2, "VALID"), (9, 3, 1, "SAME"), (11, 5, 3, "VALID")])
-def test_oracle_conv_matches_torch(H, k, s, pad):
+# square kernels and strides as the zoo has them, then anisotropic pairs (kh, kw) / (sh, sw): the first convolutions of
+# tests/support/geometry_cases.py (an odd SAME pad on one axis only, a stride larger than the kernel, a kernel taller than the image)
+CONV_CASES = [(28, 8, 2, "SAME"), (28, 5, 2, "SAME"), (14, 6, 2, "VALID"), (9, 3, 1, "SAME"), (11, 5, 3, "VALID"),
+              (9, (3, 5), (2, 3), "SAME"), (12, (2, 3), (3, 2), "VALID"), (5, (7, 2), (1, 3), "SAME")]
+
+
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def _torch_conv(xt, K, b, k, s, pad):
+    """torch's conv2d of an NCHW float64 tensor with the explicit asymmetric SAME padding; NHWC out."""
     import torch
     import torch.nn.functional as F
-    rs = np.random.RandomState(H * 10 + k)
-    x = rs.standard_normal((3, H, H + 1, 4))
-    K = rs.standard_normal((k, k, 4, 5))
-    b = rs.standard_normal(5)
-    y = CO.conv2d(x, K, b, (s, s), pad)
-    xt = torch.from_numpy(x).permute(0, 3, 1, 2)
+    (kh, kw), (sh, sw) = k, s
     if pad == "SAME":
-        _, pt, pb = CO.same_padding(H, k, s)
-        _, pl, pr = CO.same_padding(H + 1, k, s)
+        _, pt, pb = CO.same_padding(xt.shape[2], kh, sh)
+        _, pl, pr = CO.same_padding(xt.shape[3], kw, sw)
         xt = F.pad(xt, (pl, pr, pt, pb))
-    yt = F.conv2d(xt, torch.from_numpy(K).permute(3, 2, 0, 1), torch.from_numpy(b), stride=s).permute(0, 2, 3, 1).numpy()
+    return F.conv2d(xt, torch.from_numpy(K).permute(3, 2, 0, 1), torch.from_numpy(b), stride=(sh, sw)).permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("H,k,s,pad", CONV_CASES)
+def test_oracle_conv_matches_torch(H, k, s, pad):
+    import torch
+    k, s = _pair(k), _pair(s)
+    rs = np.random.RandomState(H * 10 + k[0])
+    x = rs.standard_normal((3, H, H + 1, 4))
+    K = rs.standard_normal(k + (4, 5))
+    b = rs.standard_normal(5)
+    y = CO.conv2d(x, K, b, s, pad)
+    yt = _torch_conv(torch.from_numpy(x).permute(0, 3, 1, 2), K, b, k, s, pad).numpy()
     assert y.shape == yt.shape
     np.testing.assert_allclose(y, yt, rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("H,k,s,pad", CONV_CASES)
+def test_oracle_conv_backward_input_matches_autograd(H, k, s, pad):
+    """conv2d_backward_input against torch autograd through the same padded conv2d, from a random output gradient."""
+    import torch
+    k, s = _pair(k), _pair(s)
+    rs = np.random.RandomState(H * 10 + k[1] + 1)
+    x = rs.standard_normal((3, H, H + 1, 4))
+    K = rs.standard_normal(k + (4, 5))
+    b = rs.standard_normal(5)
+    xt = torch.from_numpy(x).permute(0, 3, 1, 2).requires_grad_(True)
+    yt = _torch_conv(xt, K, b, k, s, pad)
+    g = rs.standard_normal(tuple(yt.shape))
+    (want,) = torch.autograd.grad(yt, xt, torch.from_numpy(g))
+    got = CO.conv2d_backward_input(g, K, x.shape, s, pad)
+    assert got.shape == x.shape
+    np.testing.assert_allclose(got, want.permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
 
 
 def test_model_zoo_shapes_and_names():
