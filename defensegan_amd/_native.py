@@ -66,6 +66,7 @@ SYMBOLS = [
     ("dg_jacobian_augment", _i, [_vp, _vp, _vp, _i, _f, _i, _vp, _vp]),
     ("dg_bpda_step", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp]),
     ("dg_bpda_track", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    ("dg_pgd", _i, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _f, _f, _vp, _vp, _vp]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

@@ -106,6 +106,21 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
+int clf_launch_bpda_step(const float* g, float* gsum, const float* x_cur, const float* x_orig, float* x_next, long long total,
+                         int row_elems, int accumulate_only, float eps, float eps_iter, float lo, float hi, hipStream_t s) {
+    const bool vec = row_elems % 4 == 0 && aligned16(g) && aligned16(gsum) && aligned16(x_cur) && aligned16(x_orig) && aligned16(x_next);
+    const long long nvec = vec ? total / 4 : total;
+    const unsigned grid = (unsigned)((nvec + 255) / 256);
+    if (vec)
+        hipLaunchKernelGGL(bpda_step_kernel<4>, dim3(grid), dim3(256), 0, s, g, gsum, x_cur, x_orig, x_next, nvec, accumulate_only ? 1 : 0,
+                           eps, eps_iter, lo, hi);
+    else
+        hipLaunchKernelGGL(bpda_step_kernel<1>, dim3(grid), dim3(256), 0, s, g, gsum, x_cur, x_orig, x_next, nvec, accumulate_only ? 1 : 0,
+                           eps, eps_iter, lo, hi);
+    CLF_TRY(hipGetLastError());
+    return DG_OK;
+}
+
 extern "C" {
 
 int dg_bpda_step(dg_clf* h, const float* rec, const int32_t* labels, int B, const float* x_cur, const float* x_orig, float* gsum,
@@ -124,18 +139,8 @@ int dg_bpda_step(dg_clf* h, const float* rec, const int32_t* labels, int B, cons
     clf_launch_ce_grad(h->acts[h->logit_layer], labels, h->bpda->seed, B, h->n_logits, s);
     float* g = nullptr;
     if ((rc = clf_seeded_backward(h, h->bpda->seed, B, s, &g))) return rc;
-    const long long total = (long long)B * h->pixels();
-    const bool vec = h->pixels() % 4 == 0 && aligned16(g) && aligned16(gsum) && aligned16(x_cur) && aligned16(x_orig) && aligned16(x_next);
-    const long long nvec = vec ? total / 4 : total;
-    const unsigned grid = (unsigned)((nvec + 255) / 256);
-    if (vec)
-        hipLaunchKernelGGL(bpda_step_kernel<4>, dim3(grid), dim3(256), 0, s, g, gsum, x_cur, x_orig, x_next, nvec, accumulate_only ? 1 : 0,
-                           eps, eps_iter, clip_min, clip_max);
-    else
-        hipLaunchKernelGGL(bpda_step_kernel<1>, dim3(grid), dim3(256), 0, s, g, gsum, x_cur, x_orig, x_next, nvec, accumulate_only ? 1 : 0,
-                           eps, eps_iter, clip_min, clip_max);
-    CLF_TRY(hipGetLastError());
-    return DG_OK;
+    return clf_launch_bpda_step(g, gsum, x_cur, x_orig, x_next, (long long)B * h->pixels(), h->pixels(), accumulate_only, eps, eps_iter,
+                                clip_min, clip_max, s);
 }
 
 int dg_bpda_track(const int32_t* preds, const int32_t* labels, int B, int k, const float* x_iter, float* x_best, int32_t* first_success,

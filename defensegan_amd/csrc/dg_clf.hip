@@ -367,6 +367,7 @@ int dg_clf_destroy(dg_clf* h) {
     train_release(h->tr);
     jac_release(h->jac);
     bpda_release(h->bpda);
+    pgd_release(h->pgd);
     delete h;
     return DG_OK;
 }

@@ -1,5 +1,6 @@
-// The classifier handle as its five source files see it: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
-// dg_cw.hip (the Carlini-Wagner attack), dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation) and dg_bpda.hip (the BPDA/EOT step).  Everything here is internal to the library: plain C++
+// The classifier handle as its six source files see it: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
+// dg_cw.hip (the Carlini-Wagner attack), dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation), dg_bpda.hip (the BPDA/EOT step) and dg_pgd.hip (PGD on the bare
+// classifier).  Everything here is internal to the library: plain C++
 // under hidden visibility, nothing of it is exported.
 #pragma once
 
@@ -36,6 +37,7 @@ struct CwWork;       // dg_cw.hip
 struct TrainWork;    // dg_clf_train.hip
 struct JacWork;      // dg_jacobian.hip
 struct BpdaWork;     // dg_bpda.hip
+struct PgdWork;      // dg_pgd.hip
 
 struct dg_clf {
     int device = 0;
@@ -60,6 +62,7 @@ struct dg_clf {
     TrainWork* tr = nullptr;                  // training workspace and Adam state
     JacWork* jac = nullptr;                   // class-gradient seed, grown on demand
     BpdaWork* bpda = nullptr;                 // BPDA's cross-entropy seed, grown on demand
+    PgdWork* pgd = nullptr;                   // PGD's seed and its two iterate buffers, grown on demand
 
     int pixels() const { return in_h * in_w * in_c; }
 };
@@ -107,5 +110,13 @@ void cw_release(CwWork* w);          // dg_cw.hip
 void train_release(TrainWork* w);    // dg_clf_train.hip
 void jac_release(JacWork* w);        // dg_jacobian.hip
 void bpda_release(BpdaWork* w);      // dg_bpda.hip
+void pgd_release(PgdWork* w);        // dg_pgd.hip
+
+// ---- dg_bpda.hip ----------------------------------------------------------------------------------------------------------------
+// The projected sign step over `total` elements (rows of row_elems): accumulate_only: gsum += g; otherwise t = gsum + g (t = g when
+// gsum == NULL) and x_next = clip(x_orig + clamp(x_cur + eps_iter sign(t) - x_orig, -eps, eps), lo, hi).  float4 where row_elems is
+// a multiple of 4 and every pointer given is 16-byte aligned.
+int clf_launch_bpda_step(const float* g, float* gsum, const float* x_cur, const float* x_orig, float* x_next, long long total,
+                         int row_elems, int accumulate_only, float eps, float eps_iter, float lo, float hi, hipStream_t s);
 
 #pragma GCC visibility pop

@@ -762,8 +762,8 @@ class BPDA(object):
     in ``gan_defense.model_eval_gan``.  With a USE_BN generator the rows of an engine call share its Batchnorm statistics: the
     calls are then cut on ``batch_size`` exactly, and the result DOES depend on it.
 
-    A bare model raises ValueError: projected gradient descent on an undefended classifier is out of scope here.  A reconstruction
-    layer with a fixed ``z_init`` is refused as well (the attack draws fresh latents for every projection)."""
+    A bare model raises ValueError: projected gradient descent on an undefended classifier is ``ProjectedGradientDescent``.  A
+    reconstruction layer with a fixed ``z_init`` is refused as well (the attack draws fresh latents for every projection)."""
 
     def __init__(self, model: MLP, back="tf", sess=None, ops=None):
         self.model = model
@@ -777,7 +777,7 @@ class BPDA(object):
         rl = m.rec_layer
         if rl is None:
             raise ValueError("BPDA attacks a model with the Defense-GAN projection attached (add_rec_model); projected gradient "
-                             "descent on a bare classifier (PGD-on-bare) is out of scope")
+                             "descent on a bare classifier (PGD-on-bare) is ProjectedGradientDescent")
         if rl.z_init is not None:
             raise ValueError("BPDA draws fresh latents for every projection; the reconstruction layer has a fixed z_init")
         nb_iter, mm = int(nb_iter), int(eot_samples)
@@ -845,6 +845,90 @@ class BPDA(object):
         if was_numpy:
             x_best, first_success = x_best.cpu().numpy(), first_success.cpu().numpy()
         return (x_best, first_success) if return_info else x_best
+
+
+class ProjectedGradientDescent(object):
+    """Projected gradient descent (Madry et al. 2018), L-infinity, on a BARE classifier: ``BPDA`` with the identity as the projection
+    and ``eot_samples = 1``, run as ONE asynchronous device call per ``batch_size`` images (``dg_pgd``, defensegan_amd/csrc/dg_pgd.hip):
+
+        x_0 = clip(x)            (``rand_init``: clip(x + bpda_rand_noise(...)); or ``x_init`` as given)
+        for k < nb_iter:   g_k = grad_x CE(logits(x_k), y)                     (``input_gradient``'s bits)
+                           x_{k+1} = clip(x + clamp(x_k + eps_iter sign(g_k) - x, -eps, eps), clip_min, clip_max),  sign(0) = 0
+
+    Best tracking as BPDA's: iterate k + 1 succeeds for an image when the model's prediction on it is not ``y``; ``generate``
+    returns per image the first successful iterate, or the last one; ``return_info=True`` adds ``first_success`` [n] int32 (the
+    iterate's index in 1 .. nb_iter, or -1).  The prediction is read off the logits the next iteration's forward keeps:
+    ``nb_iter + 1`` forwards and ``nb_iter`` backwards in all.
+
+    ``x`` NumPy or a device tensor [n, H, W, C] (NumPy in gives NumPy out; a tensor gives tensors on the caller's current stream,
+    not waited for); ``y`` class indices or one-hot rows, required; a class index outside [0, nb_classes) gives that image a zero
+    gradient (training's policy): it stays at x_0.  ``seed`` (default BPDA_DEFAULT_SEED) keys the ``rand_init`` draw, by the
+    image.  ``batch_size`` only bounds the images per device call (default: all): every output element is one thread's
+    fixed-order arithmetic on its own image, so the result does not depend on it, bit for bit.
+
+    A model with the reconstruction layer attached raises ValueError: the attack that uses the defense is ``BPDA``."""
+
+    def __init__(self, model: MLP, back="tf", sess=None):
+        self.model = model
+
+    def generate(self, x, y, eps=0.3, eps_iter=0.05, nb_iter=10, clip_min=None, clip_max=None, rand_init=False, seed=None, x_init=None,
+                 batch_size=None, return_info=False):
+        import torch
+        m = self.model
+        if m.rec_layer is not None:
+            raise ValueError("ProjectedGradientDescent attacks a bare classifier; this model has the Defense-GAN projection attached "
+                             "(add_rec_model), through which the gradient is identically zero: use BPDA")
+        nb_iter = int(nb_iter)
+        if nb_iter < 1:
+            raise ValueError("nb_iter must be >= 1, got %d" % nb_iter)
+        if not (float(eps) >= 0 and float(eps_iter) >= 0):
+            raise ValueError("eps and eps_iter must be >= 0")
+        if rand_init and x_init is not None:
+            raise ValueError("give rand_init or x_init, not both")
+        lo = float("-inf") if clip_min is None else float(clip_min)
+        hi = float("inf") if clip_max is None else float(clip_max)
+        if not lo <= hi:
+            raise ValueError("clip_min must not exceed clip_max")
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        seed = BPDA_DEFAULT_SEED if seed is None else int(seed)
+        m._ensure()
+        if not m._weights_set:
+            raise _native.NativeError("classifier weights not set")
+        dev = torch.device("cuda", m._device)
+        was_numpy = isinstance(x, np.ndarray)
+        to = lambda a: (torch.from_numpy(np.ascontiguousarray(a, np.float32)) if isinstance(a, np.ndarray) else a).to(device=dev, dtype=torch.float32).contiguous()
+        t = to(x)
+        if t.dim() != 4 or tuple(t.shape[1:]) != tuple(m.input_shape[1:]) or int(t.shape[0]) == 0:
+            raise ValueError("x must be [n, %s] with n > 0, got %s" % (", ".join(str(d) for d in m.input_shape[1:]), tuple(t.shape)))
+        n, P = int(t.shape[0]), int(t[0].numel())
+        yy = np.asarray(y if isinstance(y, np.ndarray) else (y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y))
+        if yy.ndim > 1:
+            yy = yy.argmax(axis=-1)                                # one-hot labels as cleverhans takes them
+        if yy.shape != (n,):
+            raise ValueError("y must be %d class indices or one-hot rows" % n)
+        lab = torch.from_numpy(np.ascontiguousarray(yy.astype(np.int32))).to(dev)
+        if x_init is not None:
+            x0 = to(x_init)
+            if tuple(x0.shape) != tuple(t.shape):
+                raise ValueError("x_init must have x's shape")
+        elif rand_init:
+            x0 = torch.clamp(t + torch.from_numpy(bpda_rand_noise(n, P, eps, seed)).to(dev).view_as(t), lo, hi)
+        else:
+            x0 = torch.clamp(t, lo, hi)
+        x_adv = torch.empty_like(t)
+        first_success = torch.empty(n, dtype=torch.int32, device=dev)
+        bs = n if batch_size is None else int(batch_size)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            for a in range(0, n, bs):
+                b = min(n, a + bs)
+                _native.check(_native.load().dg_pgd(m._handle, t[a:b].data_ptr(), x0[a:b].data_ptr(), lab[a:b].data_ptr(), b - a, float(eps),
+                                                    float(eps_iter), nb_iter, lo, hi, x_adv[a:b].data_ptr(), first_success[a:b].data_ptr(),
+                                                    stream))
+        if was_numpy:
+            x_adv, first_success = x_adv.cpu().numpy(), first_success.cpu().numpy()
+        return (x_adv, first_success) if return_info else x_adv
 
 
 def rand_fgsm_prestep(test_images, eps: float, alpha: float, min_val: float = 0.0, max_val: float = 1.0, rng=None):

@@ -1,0 +1,318 @@
+"""``python -m defensegan_amd.whitebox``: the reference's white-box flow (whitebox.py:56-306) with every tensor operation on the
+device:
+
+    whitebox    trains the classifier (cleverhans model_train; ``adv_tr`` adds FGSM inputs; ``train_on_recs`` trains on cached
+                reconstructions), attacks the ORIGINAL test images (fgsm, rand_fgsm, cw -- and pgd on a bare model, bpda on a
+                defended one, which the reference has not) and measures the accuracy on the adversarial images, through the
+                Defense-GAN projection for ``defense_gan`` (with the ROC triple)                       whitebox.py:56-233
+    main        the flags and the result files of whitebox.py:236-392
+
+    python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --defense_type none --attack_type pgd
+    python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --init_path output/gans/mnist \\
+        --defense_type defense_gan --attack_type bpda --results_dir run0
+
+Kept from the reference: ``RandomState([11, 24, 1990])`` for the training schedule; the clean accuracy on the (reconstructed) test
+split printed after every epoch; with ``defense_gan`` the reconstruction layer is attached AFTER training and BEFORE the attack
+is built, so FGSM differentiates through it, sees a zero gradient and returns ``clip(x)`` (network_builder._REC_GRADIENT_NOTE);
+``rand`` in the attack type takes one random sign step of ``alpha`` first and ``alpha`` off the budget.  Not reproduced:
+``online_training`` (NotImplementedError)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from . import config, datasets, gan_defense, network_builder, py2pickle, utils_tf
+from .blackbox import SEED, _Phase, _accuracy, _labels, load_recs, result_path
+
+ATTACKS = ("fgsm", "cw", "pgd", "bpda")
+# whitebox.py:203-209; 'feed' is TensorFlow's business
+CW_PARAMS = {"binary_search_steps": 1, "max_iterations": 100, "learning_rate": 10.0, "initial_const": 100}
+ITERATIVE_DEFAULTS = {"eps_iter": 0.05, "nb_iter": 10, "eot_samples": 1}
+PGD_CALL_IMAGES = 10000                       # images per dg_pgd call: bounds the kept activations, not the result
+
+
+def attack_kind(attack_type):
+    """None for no attack (None / 'none'), else (kind in ATTACKS, rand): ``rand`` when the type contains 'rand'
+    (whitebox.py:192), the kind by the reference's tests ('fgsm' in the type, whitebox.py:198; 'cw' exactly, :201)."""
+    if attack_type is None or str(attack_type).lower() == "none":
+        return None
+    t = str(attack_type).lower()
+    rand = "rand" in t
+    if "fgsm" in t:
+        return "fgsm", rand
+    base = t.replace("rand", "").strip("_+")
+    if base in ATTACKS and not (rand and base == "cw"):
+        return base, rand
+    raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, pgd (defense_type none / adv_tr) or bpda (defense_gan)" % (attack_type,))
+
+
+def _attack_params(kind, attack_params):
+    """The overrides ``attack_params`` holds for this attack: eps_iter / nb_iter (pgd, bpda), eot_samples (bpda), any
+    CarliniWagnerL2 parameter (cw).  Values of None and the iterative attacks' keys given to another attack are left out."""
+    given = {k: v for k, v in (attack_params or {}).items() if v is not None}
+    known = set(ITERATIVE_DEFAULTS) | set(network_builder.CarliniWagnerL2.DEFAULTS)
+    if set(given) - known:
+        raise ValueError("unknown attack_params: %s" % sorted(set(given) - known))
+    if kind == "cw":
+        return {k: v for k, v in given.items() if k in network_builder.CarliniWagnerL2.DEFAULTS}
+    keys = {"pgd": ("eps_iter", "nb_iter"), "bpda": ("eps_iter", "nb_iter", "eot_samples")}.get(kind, ())
+    return {k: given.get(k, ITERATIVE_DEFAULTS[k]) for k in keys}
+
+
+def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate=0.001, nb_epochs=10, eps=0.3, alpha=0.05,
+             online_training=False, train_on_recs=False, test_on_dev=True, attack_type="fgsm", defense_type="none", num_tests=-1,
+             num_train=-1, fgsm_eps_tr=0.15, same_init=False, recs=None, attack_params=None, seed=SEED, init_seed=0, phases=None):
+    """whitebox.py:56-233.  ``gan``: a DefenseGANBase with its generator loaded, or None (``defense_type`` 'none' and 'adv_tr' need
+    none); ``model``: the classifier's MLP (initialised with the reference's initialisers from ``init_seed`` when its weights are not
+    set); ``data`` = (train_images, train_labels, test_images, test_labels), the ORIGINAL images in generator range, labels one-hot
+    or class indices.  ``num_tests`` / ``num_train`` > 0 truncate the splits.
+
+    Training: on the originals, or -- ``defense_gan`` with ``train_on_recs`` -- on ``recs`` = (train, train_labels, test, test_labels),
+    the cached reconstructions ``rec_data_path`` points to in the reference (``train_on_recs`` without them is refused,
+    whitebox.py:90-91); after every epoch the clean accuracy on the test split of what was trained on is printed
+    (whitebox.py:126-135).  ``adv_tr`` adds FGSM(``fgsm_eps_tr``) inputs clipped to [0, 1] ([-1, 1] for CelebA).  With
+    ``attack_type`` None (or 'none') the function returns ``(training accuracy, 0, None)`` here (whitebox.py:172-173).
+
+    Attacks, always from the original test images (``eps`` the budget, ``rand``: whitebox.py:192-196 with ``alpha``, the signs drawn
+    from the training ``RandomState``):
+      fgsm, rand_fgsm   FastGradientMethod, the label the model's own prediction (whitebox.py:198-200)
+      cw                CarliniWagnerL2 with binary_search_steps 1, max_iterations 100, learning_rate 10, initial_const 100
+      pgd               ProjectedGradientDescent on the true labels: 'none' and 'adv_tr' only
+      bpda              BPDA on the true labels: 'defense_gan' only
+    ``attack_params`` overrides ``eps_iter`` (0.05), ``nb_iter`` (10), ``eot_samples`` (1) of pgd / bpda and any CarliniWagnerL2
+    parameter.  pgd with 'defense_gan' or bpda without it is a ValueError.
+
+    ``defense_gan``: the reconstruction layer is attached after training (``same_init``: with one sigma = 1 draw of
+    [batch_size * rec_rr, latent_dim] as every batch's z0), the attack is built on that model, and the accuracy comes from
+    ``gan_defense.model_eval_gan`` with ``roc_info = [labels, preds, diffs]``, diffs = mean((x_adv - rec)^2).  FGSM then sees the
+    zero gradient and returns clip(x), as in the reference.  DEVIATION for cw: the reference builds CarliniWagnerL2 on the defended
+    model as well, where the zero gradient reduces it to the tanh round trip of x at a hundred defended evaluations per batch;
+    ``CarliniWagnerL2`` refuses such a model here, so the attack is built BEFORE ``add_rec_model``, sees the bare classifier, and its
+    images are then evaluated through the projection (one printed line says so).
+
+    Returns ``(accuracy on the adversarial images, 0, roc_info or None)``.  ``test_on_dev`` and ``rec_data_path`` are the data
+    loader's business and are accepted for signature compatibility.  ``phases``: a dict that receives the seconds spent in
+    'training', 'attack' and 'evaluation' (tools/whitebox_time.py)."""
+    defense_type = defense_type or "none"
+    if defense_type not in ("none", "adv_tr", "defense_gan"):
+        raise ValueError("defense_type must be none, adv_tr or defense_gan, got %r" % (defense_type,))
+    defended = defense_type == "defense_gan"
+    if defended and gan is None:
+        raise ValueError("defense_type defense_gan needs a gan")
+    kind = attack_kind(attack_type)
+    if kind is not None:
+        if kind[0] == "pgd" and defended:
+            raise ValueError("attack_type pgd differentiates a bare classifier (defense_type none or adv_tr); with defense_gan the "
+                             "iterative attack is bpda")
+        if kind[0] == "bpda" and not defended:
+            raise ValueError("attack_type bpda needs the projection (defense_type defense_gan); on a bare classifier (%s) the "
+                             "iterative attack is pgd" % defense_type)
+        if kind[0] == "bpda" and same_init:
+            raise ValueError("attack_type bpda draws fresh latents for every projection: not with same_init")
+        extra = _attack_params(kind[0], attack_params)
+    if online_training:
+        raise NotImplementedError("online_training (training through the Defense-GAN projection) is not implemented; the reference's "
+                                  "whitebox() takes the flag and never trains through the projection either (it only enters the "
+                                  "assert of whitebox.py:90-91): train on cached reconstructions (recs=..., train_on_recs)")
+    if defended and train_on_recs and recs is None:
+        raise ValueError("train_on_recs needs the cached reconstructions (recs=...), as whitebox.py:90-91 asserts")
+
+    train_images, train_labels, test_images, test_labels = data
+    train_labels, test_labels = _labels(train_labels), _labels(test_labels)
+    rec_test_images, rec_test_labels = test_images, test_labels
+    if defended and train_on_recs:
+        train_images, train_labels, rec_test_images, rec_test_labels = recs[0], _labels(recs[1]), recs[2], _labels(recs[3])
+    if num_tests > 0:
+        test_images, test_labels = test_images[:num_tests], test_labels[:num_tests]
+        rec_test_images, rec_test_labels = rec_test_images[:num_tests], rec_test_labels[:num_tests]
+    if num_train > 0:
+        train_images, train_labels = train_images[:num_train], train_labels[:num_train]
+    is_celeba = gan is not None and "celeba" in str(gan.dataset_name or gan.arch_name)
+    min_val = -1.0 if is_celeba else 0.0
+
+    model._ensure()
+    if not model._weights_set:
+        model.init_like_reference(seed=int(init_seed))
+    dev = model._device
+
+    def evaluate():
+        print("Test accuracy on legitimate examples: %0.4f" % _accuracy(model, rec_test_images, rec_test_labels, batch_size))
+
+    rng = np.random.RandomState(utils_tf.WHITEBOX_RNG_SEED)
+    with _Phase(phases, "training", dev):
+        utils_tf.model_train(model, train_images, train_labels,
+                             args={"nb_epochs": nb_epochs, "batch_size": batch_size, "learning_rate": learning_rate}, rng=rng,
+                             adv_eps=fgsm_eps_tr if defense_type == "adv_tr" else None, adv_clip=(min_val, 1.0), evaluate=evaluate,
+                             seed=seed)
+        acc = _accuracy(model, train_images, train_labels, batch_size)
+    print("[#] Accuracy on clean examples {}".format(acc))
+    if kind is None:
+        return acc, 0, None
+    kind, rand = kind
+
+    attack = None
+    if kind == "cw" and defended:
+        attack = network_builder.CarliniWagnerL2(model)
+        print("[*] cw with defense_gan: the attack is built before the reconstruction layer is attached and sees the BARE classifier "
+              "(the reference's sees a zero gradient); its images are evaluated through the projection")
+    z_init = None
+    if defended:
+        if same_init:
+            z_init = np.random.RandomState(seed).randn(int(batch_size) * int(gan.rec_rr), int(gan.latent_dim)).astype(np.float32)
+        model.add_rec_model(gan, z_init, batch_size)
+
+    if rand:
+        test_adv_from, eps = network_builder.rand_fgsm_prestep(test_images, eps, alpha, min_val, 1.0, rng=rng)
+    else:
+        test_adv_from = test_images
+    with _Phase(phases, "attack", dev):
+        if kind == "fgsm":
+            attack = network_builder.FastGradientMethod(model)
+            par = {"eps": eps, "ord": np.inf, "clip_min": min_val, "clip_max": 1.0}
+            x_adv = utils_tf.batch_eval(lambda xb: attack.generate(xb, **par), test_adv_from, batch_size)
+        elif kind == "cw":
+            attack = attack or network_builder.CarliniWagnerL2(model)
+            x_adv = attack.generate(test_adv_from, **dict(CW_PARAMS, batch_size=batch_size, **extra))
+        elif kind == "pgd":
+            attack = network_builder.ProjectedGradientDescent(model)
+            x_adv = attack.generate(test_adv_from, test_labels, eps=eps, clip_min=min_val, clip_max=1.0, seed=seed,
+                                    batch_size=PGD_CALL_IMAGES, **extra)
+        else:
+            attack = network_builder.BPDA(model)
+            x_adv = attack.generate(test_adv_from, test_labels, eps=eps, clip_min=min_val, clip_max=1.0, seed=seed, batch_size=batch_size,
+                                    **extra)
+    with _Phase(phases, "evaluation", dev):
+        if defended:
+            correct, n, roc_info = gan_defense.model_eval_gan(gan.reconstruct, model, x_adv, test_labels, batch_size,
+                                                              rec_rr=int(gan.rec_rr), seed=seed, same_init_z=z_init)
+        else:
+            correct, n, _ = gan_defense.model_eval_gan(None, model, x_adv, test_labels, batch_size, compute_diffs=False)
+            roc_info = None
+    acc_adv = correct / float(max(n, 1))
+    print("Test accuracy on adversarial examples: %0.4f\n" % acc_adv)
+    return acc_adv, 0, roc_info
+
+
+# ---------------------------------------------------------------------------------------------------- result files, CLI
+def get_results_dir_filename(flags, gan):
+    """whitebox.py:309-341 ``_get_results_dir_filename``: (results directory, file name without the counter prefix).
+
+    DEVIATION in the ``defense_gan``-with-``rec_path`` branch: the reference formats 'Iter={}_RR={:d}_LR={:.4f}' with
+    (rec_rr, rec_lr, rec_iters) -- the values in another order than the names, and ``rec_lr``, a float since main's
+    ``float(tr_lr)``, under '{:d}', which raises ValueError in Python: the reference cannot name this file.  The name it meant is
+    written instead: Iter = rec_iters, RR = rec_rr, LR = rec_lr."""
+    results_dir = os.path.join("results", "whitebox_{}_{}".format(flags.defense_type, flags.dataset_name))
+    if flags.rec_path and flags.defense_type == "defense_gan":
+        results_dir = gan.checkpoint_dir.replace("output", "results")
+        result_file_name = "Iter={}_RR={:d}_LR={:.4f}_defense=gan".format(int(gan.rec_iters), int(gan.rec_rr), float(gan.rec_lr))
+        if not flags.train_on_recs:
+            result_file_name = "orig_" + result_file_name
+    elif flags.defense_type == "adv_tr":
+        result_file_name = "advTrEps={:.2f}".format(flags.fgsm_eps_tr)
+    else:
+        result_file_name = "nodefense_"
+    if flags.num_tests > -1:
+        result_file_name = "numtest={}_".format(flags.num_tests) + result_file_name
+    if flags.num_train > -1:
+        result_file_name = "numtrain={}_".format(flags.num_train) + result_file_name
+    result_file_name = "model={}_".format(flags.model) + result_file_name
+    result_file_name += "attack={}.txt".format(flags.attack_type)
+    return results_dir, result_file_name
+
+
+def write_results(path, accuracies):
+    """whitebox.py:295-306: the line ``str(acc) + ' ' + '0 '`` (appended) and, with roc_info, ``*_roc.pkl`` in a pickle the
+    Python-2 reference reads."""
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "a") as f:
+        f.writelines([str(accuracies[i]) + " " for i in range(2)])
+        f.write("\n")
+    print("[*] saved accuracy in {}".format(path))
+    if accuracies[2]:
+        pkl = path.replace(".txt", "_roc.pkl")
+        with open(pkl, "wb") as f:
+            py2pickle.dump(accuracies[2], f)
+        print("[*] saved roc_info in {}".format(pkl))
+
+
+def build_parser() -> argparse.ArgumentParser:
+    """The flags and defaults of whitebox.py:344-392 on top of the reconstruction flags (config.add_rec_flags), plus the
+    iterative attacks' parameters."""
+    ap = config.add_rec_flags(argparse.ArgumentParser(prog="python -m defensegan_amd.whitebox", description=__doc__.split("\n\n")[0]))
+    ap.add_argument("--data_dir", required=True, help="directory of the dataset's idx-ubyte files (mnist, f-mnist)")
+    ap.add_argument("--init_path", default=None, help="generator weights: TensorFlow checkpoint dir/prefix or .npz pack")
+    ap.add_argument("--alpha", type=float, default=0.05, help="RAND+FGSM random perturbation scale")
+    ap.add_argument("--nb_classes", type=int, default=10, help="Number of classes.")
+    ap.add_argument("--learning_rate", type=float, default=0.001, help="Learning rate for training.")
+    ap.add_argument("--nb_epochs", type=int, default=10, help="Number of epochs to train model.")
+    ap.add_argument("--lmbda", type=float, default=0.1, help="accepted and ignored, as in the reference")
+    ap.add_argument("--fgsm_eps", type=float, default=0.3, help="FGSM epsilon: the budget of every L-infinity attack.")
+    ap.add_argument("--fgsm_eps_tr", type=float, default=0.15, help="FGSM epsilon for adversarial training (a config key in the reference).")
+    ap.add_argument("--num_tests", type=int, default=-1, help="Number of test samples.")
+    ap.add_argument("--random_test_iter", type=int, default=-1, help="accepted and ignored, as in the reference")
+    ap.add_argument("--online_training", action="store_true", help="not implemented (NotImplementedError)")
+    ap.add_argument("--defense_type", default="none", choices=["none", "defense_gan", "adv_tr"], help="Type of defense")
+    ap.add_argument("--attack_type", default="none", help="Type of attack [fgsm|cw|rand_fgsm|pgd|bpda]; none: train and stop")
+    ap.add_argument("--results_dir", default=None, help="The final subdirectory of the results.")
+    ap.add_argument("--model", default="F", choices=sorted(network_builder.MODELS), help="The classifier model.")
+    ap.add_argument("--debug_dir", default="temp", help="accepted and ignored (the reference's qualitative debug output)")
+    ap.add_argument("--num_train", type=int, default=-1, help="Number of training data to load.")
+    ap.add_argument("--debug", action="store_true", help="accepted and ignored (saving reconstructions)")
+    ap.add_argument("--train_on_recs", action="store_true", help="Train the classifier on the reconstructed samples using Defense-GAN.")
+    ap.add_argument("--eps_iter", type=float, default=None, help="pgd / bpda step size (default 0.05)")
+    ap.add_argument("--nb_iter", type=int, default=None, help="pgd / bpda iterations (default 10)")
+    ap.add_argument("--eot_samples", type=int, default=None, help="bpda: projections the gradient is summed over per iteration (default 1)")
+    ap.add_argument("--seed", type=int, default=SEED, help="seed of the Dropout masks and the latent draws")
+    ap.add_argument("--init_seed", type=int, default=0, help="seed of the classifier's initial weights")
+    return ap
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    from .__main__ import resolve_cfg
+    from .gan import gan_from_config
+    cfg_path = resolve_cfg(args.cfg)
+    cfg = config.load_config(cfg_path)
+    args.dataset_name = str(cfg.get("DATASET_NAME", "mnist")).lower()
+    if args.dataset_name not in ("mnist", "f-mnist"):
+        raise SystemExit("python -m defensegan_amd.whitebox loads mnist and f-mnist; call whitebox() with your own arrays for %s"
+                         % args.dataset_name)
+    rp = config.resolve_rec_params(cfg, args)
+    gan = None
+    if args.init_path:
+        gan = gan_from_config(cfg_path, rec_rr=rp["rec_rr"], rec_iters=rp["rec_iters"], rec_lr=rp["rec_lr"])
+        gan.load_generator(args.init_path)
+        gan.checkpoint_dir = args.init_path
+    elif args.defense_type == "defense_gan":
+        raise SystemExit("--defense_type defense_gan needs the generator (--init_path)")
+    if args.defense_type == "defense_gan" and not args.rec_path and args.train_on_recs:
+        raise SystemExit("--train_on_recs needs --rec_path (whitebox.py:259)")
+    batch_size = rp["batch_size"]                                          # FLAGS.batch_size: --batch_size, else the cfg's BATCH_SIZE
+    x_tr, y_tr = datasets.load_mnist_split(args.data_dir, "train")
+    x_te, y_te = datasets.load_mnist_split(args.data_dir, "test")          # test_on_dev=True selects the TEST split
+    x_tr, x_te = datasets.to_generator_range(x_tr, args.dataset_name), datasets.to_generator_range(x_te, args.dataset_name)
+    if args.num_train > 0:
+        x_tr, y_tr = x_tr[:args.num_train], y_tr[:args.num_train]
+    if args.num_tests > 0:
+        x_te, y_te = x_te[:args.num_tests], y_te[:args.num_tests]
+    # the reconstructions of the arrays as truncated above, and only where they are trained on: whitebox() reads them nowhere else
+    recs = None
+    if args.rec_path and args.defense_type == "defense_gan" and args.train_on_recs:
+        recs = load_recs(gan, args.rec_path, {"train": (x_tr, y_tr), "test": (x_te, y_te)}, batch_size=batch_size)
+    model = network_builder.MODELS[args.model](input_shape=(None,) + tuple(x_tr.shape[1:]), nb_classes=args.nb_classes)
+    results_dir, name = get_results_dir_filename(args, gan)
+    path = result_path(results_dir, name, args.results_dir)
+    accuracies = whitebox(gan, model, (x_tr, y_tr, x_te, y_te), rec_data_path=args.rec_path, batch_size=batch_size,
+                          learning_rate=args.learning_rate, nb_epochs=args.nb_epochs, eps=args.fgsm_eps, alpha=args.alpha,
+                          online_training=args.online_training, train_on_recs=args.train_on_recs, attack_type=args.attack_type,
+                          defense_type=args.defense_type, num_tests=args.num_tests, num_train=args.num_train,
+                          fgsm_eps_tr=args.fgsm_eps_tr, same_init=args.same_init, recs=recs,
+                          attack_params={"eps_iter": args.eps_iter, "nb_iter": args.nb_iter, "eot_samples": args.eot_samples},
+                          seed=args.seed, init_seed=args.init_seed)
+    write_results(path, accuracies)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

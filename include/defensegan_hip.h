@@ -395,6 +395,22 @@ int dg_bpda_track(const int32_t* preds, const int32_t* labels, int B, int k, con
                   int32_t* first_success, int64_t row_elems, void* stream);
 
 /*
+ * Projected gradient descent (L-infinity) on the BARE classifier: BPDA above with the identity as the projection and one sample,
+ * the whole attack enqueued by this one call (defensegan_amd/csrc/dg_pgd.hip's header comment and DESIGN.md section 7;
+ * network_builder.ProjectedGradientDescent).  x [B,H,W,C] the original images, x_start [B,H,W,C] the iterate x_0 (the caller's
+ * clip(x), or any start), labels [B] int32.  For k < nb_iter: g_k = d CE(softmax(logits(x_k)), labels) / dx with the bits of
+ * dg_clf_input_gradient (a label outside [0, classes) gives a zero gradient instead) and
+ *   x_{k+1} = clip(x + clamp(x_k + eps_iter * sign(g_k) - x, -eps, eps), clip_min, clip_max),  sign(0) = 0.
+ * Iterate j = 1 .. nb_iter succeeds for an image when the model's first arg-max on it is not its label; x_adv [B,H,W,C] receives
+ * per image the first successful iterate or else the last one, first_success [B] int32 that j or -1.  nb_iter + 1 forwards and
+ * nb_iter backwards.  x_adv must not be x or x_start.  nb_iter < 1, eps < 0, eps_iter < 0 and clip_min > clip_max are
+ * DG_E_INVALID.  Device pointers; asynchronous on `stream`, no host synchronisation, no graph capture, no atomics; the result
+ * does not depend on how many images share a call.
+ */
+int dg_pgd(dg_clf* h, const float* x, const float* x_start, const int32_t* labels, int B, float eps, float eps_iter, int nb_iter,
+           float clip_min, float clip_max, float* x_adv, int32_t* first_success, void* stream);
+
+/*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
  * (no collective on the data path) and ONE all_gather assembles the evaluation message -- per rank `count` int32 words, e.g.
  * [n | labels (cap) | preds (cap) | diffs (cap, float32 bits)] as defensegan_amd/gan_defense.py:model_eval_gan_sharded builds it
