@@ -100,9 +100,13 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
 // backward: stats[0][c] = mean(dy), stats[1][c] = mean(dy * xhat)
 // 16 channels per workgroup, 16 threads per channel: thread j of a channel adds blocks j, j+16, ... (4 loads in flight), the
 // 16 sums are folded in LDS in a fixed order.
+// blk_rows (forward block sums of a GEMM epilogue only): the second record of block b is its sum of squares about its OWN mean
+// and blk_rows[b] its row count n_b; sum x^2 over the block = M2_b + s1_b^2 / n_b is put together here in float64, where
+// E[x^2] - mean^2 has the digits to spare that the float32 block sum of x^2 did not have (Chan et al.'s pairwise merge
+// M2 = sum M2_b + sum n_b (mean_b - mean)^2, written as one pass)
 template <typename PartT>          // double: bn_partial_kernel's sums; float: the GEMM epilogue's per-32-row-block sums (EPI_BIAS_STATS)
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const PartT* __restrict__ part, int nblk, long long rows, int C,
-                                                          float* __restrict__ stats, int forward, const float* __restrict__ shift = nullptr) {
+                                                          float* __restrict__ stats, int forward, const float* __restrict__ blk_rows = nullptr) {
     __shared__ double red[2][256];
     const int tid = threadIdx.x;
     const int cl = tid & 15, j = tid >> 4;
@@ -116,13 +120,16 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const PartT* __restric
             for (int u = 0; u < 4; ++u) {
                 x1[u] = (double)part[((long long)(k + u * BN_FSPLIT) * 2 + 0) * C + c];
                 x2[u] = (double)part[((long long)(k + u * BN_FSPLIT) * 2 + 1) * C + c];
+                if (blk_rows) x2[u] += x1[u] * x1[u] / (double)blk_rows[k + u * BN_FSPLIT];
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) { s1 += x1[u]; s2 += x2[u]; }
         }
         for (; k < nblk; k += BN_FSPLIT) {
-            s1 += (double)part[((long long)k * 2 + 0) * C + c];
+            const double x1 = (double)part[((long long)k * 2 + 0) * C + c];
+            s1 += x1;
             s2 += (double)part[((long long)k * 2 + 1) * C + c];
+            if (blk_rows) s2 += x1 * x1 / (double)blk_rows[k];
         }
     }
     red[0][tid] = s1; red[1][tid] = s2;
@@ -133,8 +140,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const PartT* __restric
     if (forward) {
         double var = m2 - m1 * m1;
         if (var < 0.0) var = 0.0;
-        // (block sums of the GEMM epilogue are taken before the bias: shift[c] puts it back; the variance does not see it)
-        stats[c] = (float)(m1 + (shift ? (double)shift[c] : 0.0));
+        stats[c] = (float)m1;
         stats[C + c] = (float)(1.0 / sqrt(var + 1e-5));
     } else {
         stats[c] = (float)m1;
@@ -197,7 +203,7 @@ static void launch_bn_stats(const float* a, const float* b, const BnArgs& args, 
     if (b) hipLaunchKernelGGL(bn_partial_kernel<true>, grid, dim3(256), 0, s, a, b, (const float*)args.fstats, args.part, (long long)args.rows, args.C, rpb);
     else hipLaunchKernelGGL(bn_partial_kernel<false>, grid, dim3(256), 0, s, a, b, (const float*)nullptr, args.part, (long long)args.rows, args.C, rpb);
     hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3((args.C + 15) / 16), dim3(256), 0, s, (const double*)args.part, nblk, (long long)args.rows,
-                       args.C, stats, forward);
+                       args.C, stats, forward, (const float*)nullptr);
 }
 
 void launch_bn_forward(const BnArgs& a, int relu, hipStream_t s) {
@@ -211,8 +217,9 @@ void launch_bn_forward(const BnArgs& a, int relu, hipStream_t s) {
 // per-32-row-block sums (thousands of blocks for a 14x14 map) folded to at most BN_FOLD_RANGES float64 partials, coalesced over
 // the channels, before the per-channel finalize (which has C / 16 workgroups only)
 constexpr int BN_FOLD_RANGES = 256;
+// blk_rows: as in bn_finalize_kernel -- the partials then hold sum x and sum x^2 (float64), which is what it expects of them
 __global__ __launch_bounds__(256) void bn_fold_blocks_kernel(const float* __restrict__ sums, double* __restrict__ part, int nblk, int C,
-                                                            int blocks_per_range) {
+                                                            int blocks_per_range, const float* __restrict__ blk_rows) {
     // thread = one float4 of the [2][C] record of a block; the 2C/4 quads of a record sit on adjacent lanes, the other lanes of
     // the workgroup take other blocks of the range
     const int quads = (2 * C) / 4;
@@ -228,6 +235,12 @@ __global__ __launch_bounds__(256) void bn_fold_blocks_kernel(const float* __rest
         for (int b = b0 + bl; b < b1; b += lanes) {
             const float4 v = *reinterpret_cast<const float4*>(sums + (long long)b * 2 * C + 4 * q);
             acc[0] += (double)v.x; acc[1] += (double)v.y; acc[2] += (double)v.z; acc[3] += (double)v.w;
+            if (blk_rows && 4 * q >= C) {                  // a quad of the second record: + s1^2 / n_b of the same columns
+                const float4 s = *reinterpret_cast<const float4*>(sums + (long long)b * 2 * C + 4 * q - C);
+                const double n = (double)blk_rows[b];
+                acc[0] += (double)s.x * (double)s.x / n; acc[1] += (double)s.y * (double)s.y / n;
+                acc[2] += (double)s.z * (double)s.z / n; acc[3] += (double)s.w * (double)s.w / n;
+            }
         }
     }
     if (lanes > 1) {
@@ -249,29 +262,29 @@ __global__ __launch_bounds__(256) void bn_fold_blocks_kernel(const float* __rest
 // mean / rstd (forward) or mean(dy) / mean(dy * xhat) from nblk float block sums.  More than BN_FOLD_RANGES blocks are first folded
 // to that many float64 partials (coalesced over the channels); fewer go to the finalize kernel as they are -- the same additions in
 // the same order (a range would hold one block), one launch less (BN1: 80 blocks at 2560 rows; the MNIST tail: one per workgroup)
-static void stats_from_blocks(const BnArgs& a, const float* block_sums, int nblk, float* stats, int forward, const float* shift, hipStream_t s);
+static void stats_from_blocks(const BnArgs& a, const float* block_sums, const float* blk_rows, int nblk, float* stats, int forward, hipStream_t s);
 
 // block sums -> at most BN_FOLD_RANGES float64 partials in a.part; returns the number of ranges
-static int fold_blocks(const BnArgs& a, const float* block_sums, int nblk, hipStream_t s) {
+static int fold_blocks(const BnArgs& a, const float* block_sums, const float* blk_rows, int nblk, hipStream_t s) {
     const int per_range = (nblk + BN_FOLD_RANGES - 1) / BN_FOLD_RANGES;
     const int ranges = (nblk + per_range - 1) / per_range;
     const int quads = (2 * a.C) / 4;
-    hipLaunchKernelGGL(bn_fold_blocks_kernel, dim3((unsigned)ranges, (unsigned)((quads + 255) / 256)), dim3(256), 0, s, block_sums, a.part, nblk, a.C, per_range);
+    hipLaunchKernelGGL(bn_fold_blocks_kernel, dim3((unsigned)ranges, (unsigned)((quads + 255) / 256)), dim3(256), 0, s, block_sums, a.part, nblk, a.C, per_range, blk_rows);
     return ranges;
 }
 
-static void stats_from_blocks(const BnArgs& a, const float* block_sums, int nblk, float* stats, int forward, const float* shift, hipStream_t s) {
+static void stats_from_blocks(const BnArgs& a, const float* block_sums, const float* blk_rows, int nblk, float* stats, int forward, hipStream_t s) {
     if (nblk <= BN_FOLD_RANGES) {
-        hipLaunchKernelGGL(bn_finalize_kernel<float>, dim3((a.C + 15) / 16), dim3(256), 0, s, block_sums, nblk, (long long)a.rows, a.C, stats, forward, shift);
+        hipLaunchKernelGGL(bn_finalize_kernel<float>, dim3((a.C + 15) / 16), dim3(256), 0, s, block_sums, nblk, (long long)a.rows, a.C, stats, forward, blk_rows);
         return;
     }
-    const int ranges = fold_blocks(a, block_sums, nblk, s);
+    const int ranges = fold_blocks(a, block_sums, blk_rows, nblk, s);
     hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3((a.C + 15) / 16), dim3(256), 0, s, (const double*)a.part, ranges, (long long)a.rows, a.C, stats, forward,
-                       shift);
+                       (const float*)nullptr);
 }
 
-void launch_bn_forward_from_blocks(const BnArgs& a, const float* block_sums, int nblk, int relu, hipStream_t s, const float* shift) {
-    stats_from_blocks(a, block_sums, nblk, a.fstats, 1, shift, s);
+void launch_bn_forward_from_blocks(const BnArgs& a, const float* block_sums, const float* block_rows, int nblk, int relu, hipStream_t s) {
+    stats_from_blocks(a, block_sums, block_rows, nblk, a.fstats, 1, s);
     if (relu < 0) return;              // statistics only: the consumer applies relu(bn(.)) itself (the MNIST tail's Batchnorm form)
     const long long total = (long long)a.rows * a.C;
     hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, a.a, a.xhat, a.fstats,
@@ -279,7 +292,7 @@ void launch_bn_forward_from_blocks(const BnArgs& a, const float* block_sums, int
 }
 
 void launch_bn_backward_from_blocks(const BnArgs& a, const float* block_sums, int nblk, hipStream_t s) {
-    stats_from_blocks(a, block_sums, nblk, a.bstats, 0, nullptr, s);
+    stats_from_blocks(a, block_sums, nullptr, nblk, a.bstats, 0, s);
     const long long total = (long long)a.rows * a.C;
     hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, a.a, a.xhat, a.fstats,
                        a.bstats, a.scale, total, a.C);

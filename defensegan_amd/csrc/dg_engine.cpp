@@ -118,7 +118,7 @@ void free_workspace(dg_handle* h) {
     for (auto& a : h->act) fr(a);
     for (auto& a : h->actf) fr(a);
     for (auto& g : h->gate) if (g) { (void)hipFree(g); g = nullptr; }
-    for (auto& a : h->ai) { a.buf = nullptr; fr(a.xhat); fr(a.block_sums); a.block_cap = 0; }
+    for (auto& a : h->ai) { a.buf = nullptr; fr(a.xhat); fr(a.block_sums); a.block_rows = nullptr; a.block_cap = 0; }
     if (h->bn_part) { (void)hipFree(h->bn_part); h->bn_part = nullptr; }
     fr(h->tail_bn_sums); h->tail_bn_sums_wgs = 0;
     if (h->upd_count) { (void)hipFree(h->upd_count); h->upd_count = nullptr; }
@@ -179,7 +179,9 @@ int ensure_workspace(dg_handle* h, int64_t rows) {
                 // sums are consumed right behind the forward GEMM)
                 if (d + 1 < nd && h->Bd[(size_t)d].mode == dg::EPI_MASK_STATS)
                     blocks = std::max(blocks, (size_t)dg::stat_blocks(h->Bd[(size_t)d].bplan, (int)std::min<int64_t>(cap, 1 << 24)));
-                HIP_TRY(hipMalloc(&a.block_sums, blocks * 2 * (size_t)a.bn_C * sizeof(float)));
+                // (+ one float per block behind the records: the row count of each forward block, GemmArgs::stats_rows)
+                HIP_TRY(hipMalloc(&a.block_sums, (blocks * 2 * (size_t)a.bn_C + blocks) * sizeof(float)));
+                a.block_rows = a.block_sums + blocks * 2 * (size_t)a.bn_C;
                 a.block_cap = (int64_t)blocks;
             }
             const size_t need = (size_t)dg::bn_max_blocks() * 2 * a.bn_C;
@@ -192,9 +194,10 @@ int ensure_workspace(dg_handle* h, int64_t rows) {
         HIP_TRY(hipMalloc(&h->tail_bn_sums, (size_t)h->tail_pipe * 2 * (size_t)h->ai[(size_t)nd - 1].bn_C * sizeof(float)));
         h->tail_bn_sums_wgs = h->tail_pipe;
     }
-    h->F1.stats = h->ai[0].block_sums; h->F1.stats_cap = h->ai[0].block_cap;
+    h->F1.stats = h->ai[0].block_sums; h->F1.stats_cap = h->ai[0].block_cap; h->F1.stats_rows = h->ai[0].block_rows;
     for (int d = 0; d + 1 < nd; ++d) {
         h->Fd[(size_t)d].stats = h->ai[d + 1].block_sums; h->Fd[(size_t)d].stats_cap = h->ai[d + 1].block_cap;
+        h->Fd[(size_t)d].stats_rows = h->ai[d + 1].block_rows;
         h->Bd[(size_t)d].stats = h->ai[d].block_sums; h->Bd[(size_t)d].stats_cap = h->ai[d].block_cap;
     }
     h->cap_rows = cap;
@@ -560,8 +563,8 @@ int run_forward(dg_handle* h, const float* x, const RowGroup& g, int R, bool wan
     auto bn_forward = [&](int d, const GemmOp& producer) {
         ProfScope ps(h, s, prof, "BNf", 0.0);
         if (producer.mode == dg::EPI_BIAS_STATS)
-            dg::launch_bn_forward_from_blocks(bn_args(h, h->ai[d], n_rows), h->ai[d].block_sums, (int)dg::stat_blocks(producer.bplan, n_rows),
-                                              (tail_bn && d == nd - 1) ? -1 : 1, s, producer.bias);
+            dg::launch_bn_forward_from_blocks(bn_args(h, h->ai[d], n_rows), h->ai[d].block_sums, h->ai[d].block_rows, (int)dg::stat_blocks(producer.bplan, n_rows),
+                                              (tail_bn && d == nd - 1) ? -1 : 1, s);
         else
             dg::launch_bn_forward(bn_args(h, h->ai[d], n_rows), 1, s);
     };
@@ -741,11 +744,13 @@ int rebuild_plans(dg_handle* h) {
     h->F1.W = h->lin_wt; h->F1.bias = h->lin_b;
     h->F1.stats = h->ai.empty() ? nullptr : h->ai[0].block_sums;
     h->F1.stats_cap = h->ai.empty() ? 0 : h->ai[0].block_cap;
+    h->F1.stats_rows = h->ai.empty() ? nullptr : h->ai[0].block_rows;
     h->B1.W = h->lin_w;
     for (size_t d = 0; d + 1 < ndec; ++d) {
         h->Fd[d].W = h->F[d]; h->Fd[d].bias = h->bias[d];
         h->Fd[d].stats = h->ai[d + 1].block_sums;
         h->Fd[d].stats_cap = h->ai[d + 1].block_cap;
+        h->Fd[d].stats_rows = h->ai[d + 1].block_rows;
         h->Bd[d].W = h->Ft[d];
         h->Bd[d].stats = h->ai[d].block_sums;
         h->Bd[d].stats_cap = h->ai[d].block_cap;

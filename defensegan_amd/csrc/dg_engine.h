@@ -59,6 +59,7 @@ struct ActInfo {
     float* fstats = nullptr;  // [2, bn_C]
     float* bstats = nullptr;  // [2, bn_C]
     float* block_sums = nullptr;  // [blocks][2][bn_C]: per-32-row-block column sums left by the producing GEMM's epilogue (EPI_BIAS_STATS)
+    float* block_rows = nullptr;  // [blocks]: rows of each forward block, behind the records in the same allocation
     int64_t block_cap = 0;        // blocks block_sums holds
 };
 
@@ -104,6 +105,7 @@ struct GemmOp {
     const float* W = nullptr;
     const float* bias = nullptr;
     float* stats = nullptr;   // EPI_BIAS_STATS / EPI_MASK_STATS: the block sums of the activation this layer writes (ActInfo::block_sums)
+    float* stats_rows = nullptr;  // EPI_BIAS_STATS: the row count of every block (ActInfo::block_rows)
     int64_t stats_cap = 0;    // blocks that buffer holds
     int bn_act = -1;          // EPI_MASK_STATS: index (dg_handle::ai) of the activation whose ReLU gradient this layer writes
 };

@@ -71,6 +71,7 @@ dg::GemmArgs gemm_args(dg_handle* h, const GemmOp& op, const JobList& jl, const 
     a.kch = op.bplan.kch;
     a.mode = op.mode;
     a.stats = op.stats;
+    a.stats_rows = op.stats_rows;
     a.stats_cols = op.bplan.ncols;
     a.gate_bits = nullptr;
     a.gate_words = 0;

@@ -33,6 +33,15 @@ int64_t dg_debug_read(dg_handle* h, const char* what, float* dst, int64_t n) {
             return cnt;
         }
     }
+    else if ((w.size() == 6 && w.compare(0, 5, "bnpre") == 0) || (w.size() == 4 && (w.compare(0, 3, "bnf") == 0 || w.compare(0, 3, "bnb") == 0))) {
+        // Batchnorm layer d: the pre-activations its producing GEMM left, its forward / backward statistics [2][bn_C]
+        const int d = w.back() - '0';
+        if (d >= 0 && d < (int)h->ai.size() && h->ai[(size_t)d].has_bn) {
+            const ActInfo& a = h->ai[(size_t)d];
+            if (w.size() == 6) { src = a.xhat; avail = a.xhat ? h->cap_rows * a.row_floats : 0; }
+            else { src = w[2] == 'f' ? a.fstats : a.bstats; avail = src ? 2 * (int64_t)a.bn_C : 0; }
+        }
+    }
     if (!src) return fail(DG_E_INVALID, "unknown buffer '%s'", what);
     const int64_t cnt = n < avail ? n : avail;
     HIP_TRY(hipMemcpy(dst, src, (size_t)cnt * sizeof(float), hipMemcpyDeviceToDevice));

@@ -376,13 +376,12 @@ __device__ __forceinline__ void run_job(const GemmArgs& g, const JobDesc jb, cha
                 f32x4 v = *reinterpret_cast<const f32x4*>(tb + (p * 8 + er) * 32 + ec);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    // EPI_BIAS_STATS: the sums are taken of the accumulator BEFORE the bias (launch_bn_forward_from_blocks adds it back to
-                    // the mean in float64): the float32 block sums of x and x^2 then carry no bias-sized offset, which
-                    // E[x^2] - mean^2 would have to cancel
-                    if constexpr (MODE == EPI_BIAS_STATS) {
-                        if (ovalid[i][p]) { s1[q] += v[q]; s2[q] = __builtin_fmaf(v[q], v[q], s2[q]); }
-                    }
                     float t = v[q] + bv[q];
+                    // EPI_BIAS_STATS: the sums are taken of the value that is STORED (the statistics are those of the very floats
+                    // the apply pass normalises).  The squares follow below, once the block's mean is known
+                    if constexpr (MODE == EPI_BIAS_STATS) {
+                        if (ovalid[i][p]) s1[q] += t;
+                    }
                     if constexpr (MODE == EPI_BIAS_RELU) t = t > 0.f ? t : 0.f;
                     if constexpr (MODE == EPI_MASK) t = oldv[i][j][p][q] > 0.f ? t : 0.f;
                     if constexpr (MODE == EPI_MASK_BITS) t = ((gatew[i][j][p] >> (ec + q)) & 1u) ? t : 0.f;
@@ -399,17 +398,43 @@ __device__ __forceinline__ void run_job(const GemmArgs& g, const JobDesc jb, cha
             if constexpr (MODE == EPI_BIAS_STATS || MODE == EPI_MASK_STATS) {
                 // the 8 lanes that share this lane's 4 columns hold the other rows of the 32-row block (er = lane >> 3): a fixed
                 // xor tree over lane bits 3..5, the same for every job shape -- a block's sums do not depend on the job list
+                const int row0 = wm * (BM / WM) + i * 32;                     // first row of this wave's 32-row block inside the job
+                const int nb = m_valid - row0 < 32 ? m_valid - row0 : 32;     // rows of the block (the last block of a class may be partial)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
 #pragma unroll
-                    for (int m = 8; m < 64; m <<= 1) { s1[q] += __shfl_xor(s1[q], m, 64); s2[q] += __shfl_xor(s2[q], m, 64); }
+                    for (int m = 8; m < 64; m <<= 1) s1[q] += __shfl_xor(s1[q], m, 64);
                 }
-                const int row0 = wm * (BM / WM) + i * 32;                     // first row of this wave's 32-row block inside the job
+                if constexpr (MODE == EPI_BIAS_STATS) {
+                    // The second record is the sum of squares ABOUT THE BLOCK'S OWN MEAN (the tile is still in tb): a float32 sum of
+                    // x^2 cannot resolve a variance that is small against mean^2 (rows that lie close together: the restarts of one
+                    // image late in a projection), E[x^2] - mean^2 would cancel to rounding noise.  The finalize merges the blocks
+                    // in float64 (dg_bn.hip) with the block's row count from g.stats_rows.
+                    const float inv = 1.f / (float)(nb > 0 ? nb : 1);
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(tb + (p * 8 + er) * 32 + ec);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const float dlt = (v[q] + bv[q]) - s1[q] * inv;
+                            if (ovalid[i][p]) s2[q] = __builtin_fmaf(dlt, dlt, s2[q]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+#pragma unroll
+                    for (int m = 8; m < 64; m <<= 1) s2[q] += __shfl_xor(s2[q], m, 64);
+                }
                 if (er == 0 && row0 < m_valid) {
                     const long long blk = (long long)jb.stat_base + ((jb.n_first * s_cnt + jb.j_first + row0) >> 5);
                     float* sp = g.stats + (blk * 2) * g.stats_cols + jb.n0 + col;
                     *reinterpret_cast<f32x4*>(sp) = s1;
                     *reinterpret_cast<f32x4*>(sp + g.stats_cols) = s2;
+                    if constexpr (MODE == EPI_BIAS_STATS) {
+                        // (every column tile of the block writes the same value)
+                        if (lane == 0 && j == 0) g.stats_rows[blk] = (float)nb;
+                    }
                 }
             }
         }

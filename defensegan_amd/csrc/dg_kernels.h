@@ -39,8 +39,9 @@ enum EpiMode : int {
     EPI_BIAS = 1,        // out = acc + bias[col]
     EPI_BIAS_RELU = 2,   // out = max(acc + bias[col], 0)          (BiasAdd + Relu)
     EPI_MASK = 3,        // out = out_old > 0 ? acc : 0            (ReluGrad, in place over the activation)
-    EPI_BIAS_STATS = 4,  // out = acc + bias[col], and per 32-row block of the class's M axis the column sums of out and out^2
-                         // (GemmArgs::stats): the Batchnorm forward statistics without a pass over the pre-activations
+    EPI_BIAS_STATS = 4,  // out = acc + bias[col], and per 32-row block of the class's M axis the column sums of out and of its squared
+                         // distance from the block's own mean (GemmArgs::stats, stats_rows): the Batchnorm forward statistics without
+                         // a pass over the pre-activations
     EPI_MASK_BITS = 5,   // out = gate bit ? acc : 0: ReluGrad with the gates as one bit per element (GemmArgs::gate_bits) -- the
                          // fragment-order path, whose forward activations do not live in the buffer the gradient is written to
     EPI_MASK_STATS = 6,  // ReluGrad behind a Batchnorm layer, with that layer's BACKWARD sums: the gate is re-formed from the layer's
@@ -79,7 +80,10 @@ struct GemmArgs {
     unsigned* pair_count;
     // EPI_BIAS_STATS: [blocks][2][stats_cols] floats; block = JobDesc::stat_base + (row of the class's M axis) / 32 -- a fixed
     // partition of the layer's rows whatever the job list looks like, every block summed in a fixed order: deterministic
+    // The two records of a block: EPI_BIAS_STATS the column sums of x = the stored acc + bias and of (x - block mean)^2, with the
+    // block's row count in stats_rows[block]; EPI_MASK_STATS the column sums of dy and dy * xhat.
     float* stats;
+    float* stats_rows;       // EPI_BIAS_STATS: [blocks] rows of each block (32, or fewer in the last block of a class)
     int stats_cols;          // output columns per position (the Batchnorm channels)
     // EPI_MASK_BITS: [rows][gate_words] words, bit f % 32 of word f / 32 = (activation f of the row > 0); gate_words = out_rowstride / 32
     const unsigned* gate_bits;
@@ -302,11 +306,11 @@ struct BnArgs {
 int bn_max_blocks();        // row blocks of the partial sums, upper bound: part holds bn_max_blocks() * 2 * C doubles
 void launch_bn_forward(const BnArgs& a, int relu, hipStream_t s);
 // the forward pass when the GEMM epilogue (EPI_BIAS_STATS) has left per-block column sums in `block_sums` [nblk][2][C] (float):
-// finalize (float64) + apply -- no pass over the pre-activations for the statistics.  The block sums are those of (pre - shift[c]):
-// the producing GEMM takes them before it adds its bias (shift = that bias, per column), so that the float32 sums of x and x^2
-// carry no bias-sized offset
+// finalize (float64) + apply -- no pass over the pre-activations for the statistics.  Per block the sum of the stored
+// pre-activations and their sum of squares about the block's own mean, with the block's row count in `block_rows` [nblk]; the
+// blocks are merged in float64
 // relu < 0: statistics only (a.fstats), nothing is applied -- the consumer of the layer does that itself
-void launch_bn_forward_from_blocks(const BnArgs& a, const float* block_sums, int nblk, int relu, hipStream_t s, const float* shift);
+void launch_bn_forward_from_blocks(const BnArgs& a, const float* block_sums, const float* block_rows, int nblk, int relu, hipStream_t s);
 void launch_bn_backward(const BnArgs& a, hipStream_t s);
 // the backward pass when the producer of dy (a GEMM epilogue in EPI_MASK_STATS, or the MNIST tail in its Batchnorm form) has left
 // per-block column sums of dy and dy * xhat in `block_sums` [nblk][2][C] (float): fold + finalize (float64) + apply

@@ -157,7 +157,12 @@ int dg_profile_read(dg_handle* h, int i, char* name, int name_len, int64_t* laun
 int dg_profile_reset(dg_handle* h);
 
 /* Copies an internal activation buffer of the last forward ("h1","h2","h3","h5" ...) to `dst`
- * (device pointer, capacity n floats); returns the number of floats copied.  Test hook only. */
+ * (device pointer, capacity n floats); returns the number of floats copied.  Test hook only.
+ * Names: "z", "m", "loss", "y", "part", "act<d>" (activation buffer d; after a backward pass it holds that layer's gradient), and
+ * with use_bn, for the Batchnorm layer behind activation d:
+ *   "bnpre<d>"  the pre-activations the producing GEMM left ([rows][floats per row of act<d>])
+ *   "bnf<d>"    [2][bn_C] forward statistics: mean, rstd = 1 / sqrt(biased variance + 1e-5)
+ *   "bnb<d>"    [2][bn_C] backward statistics of the last backward pass: mean(dy), mean(dy * xhat) */
 int64_t dg_debug_read(dg_handle* h, const char* what, float* dst, int64_t n);
 
 /*
