@@ -67,6 +67,10 @@ SYMBOLS = [
     ("dg_bpda_step", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp]),
     ("dg_bpda_track", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     ("dg_pgd", _i, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _f, _f, _vp, _vp, _vp]),
+    ("dg_fgm", _i, [_vp, _vp, _vp, _i, _f, _i, _f, _f, _vp, _vp]),
+    ("dg_bpda_step_ball", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _f, _f, _vp, _vp]),
+    ("dg_pgd_ball", _i, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _i, _f, _f, _vp, _vp, _vp]),
+    ("dg_row_norms", _i, [_vp, _vp, _i, _i64, _i, _vp, _vp]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

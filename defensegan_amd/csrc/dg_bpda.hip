@@ -40,9 +40,7 @@ __device__ __forceinline__ float bpda_next(float g, float xc, float xo, float ep
     const float sgn = g > 0.f ? 1.f : (g < 0.f ? -1.f : 0.f);
     float d = (xc + eps_iter * sgn) - xo;
     d = d < -eps ? -eps : (d > eps ? eps : d);
-    float v = xo + d;
-    v = v < lo ? lo : v;
-    return v > hi ? hi : v;
+    return clf_clip(xo + d, lo, hi);
 }
 
 // The step, elementwise over V-wide vectors (V = 4: float4 loads and stores; V = 1 where H W C is no multiple of 4 or a
@@ -102,13 +100,11 @@ __global__ __launch_bounds__(256) void bpda_track_kernel(const int32_t* __restri
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 int clf_launch_bpda_step(const float* g, float* gsum, const float* x_cur, const float* x_orig, float* x_next, long long total,
                          int row_elems, int accumulate_only, float eps, float eps_iter, float lo, float hi, hipStream_t s) {
-    const bool vec = row_elems % 4 == 0 && aligned16(g) && aligned16(gsum) && aligned16(x_cur) && aligned16(x_orig) && aligned16(x_next);
+    const bool vec = row_elems % 4 == 0 && clf_aligned16(g) && clf_aligned16(gsum) && clf_aligned16(x_cur) && clf_aligned16(x_orig) && clf_aligned16(x_next);
     const long long nvec = vec ? total / 4 : total;
     const unsigned grid = (unsigned)((nvec + 255) / 256);
     if (vec)
@@ -121,15 +117,15 @@ int clf_launch_bpda_step(const float* g, float* gsum, const float* x_cur, const 
     return DG_OK;
 }
 
-extern "C" {
-
-int dg_bpda_step(dg_clf* h, const float* rec, const int32_t* labels, int B, const float* x_cur, const float* x_orig, float* gsum,
-                 int accumulate_only, float eps, float eps_iter, float clip_min, float clip_max, float* x_next, void* stream) {
-    if (!h || !rec || !labels || B <= 0) return clf_fail(DG_E_INVALID, "dg_bpda_step: bad argument");
+// dg_bpda_step and dg_bpda_step_ball: the gradient chain, then gsum += g, or the projected sign step, or (ball) dg_ball.hip's L2 step.
+static int bpda_step_run(const char* who, bool ball, dg_clf* h, const float* rec, const int32_t* labels, int B, const float* x_cur,
+                         const float* x_orig, float* gsum, int accumulate_only, float eps, float eps_iter, float clip_min, float clip_max,
+                         float* x_next, void* stream) {
+    if (!h || !rec || !labels || B <= 0) return clf_fail(DG_E_INVALID, "%s: bad argument", who);
     if (accumulate_only ? !gsum : (!x_cur || !x_orig || !x_next))
-        return clf_fail(DG_E_INVALID, "dg_bpda_step: %s", accumulate_only ? "accumulate_only needs gsum" : "the step needs x_cur, x_orig and x_next");
+        return clf_fail(DG_E_INVALID, "%s: %s", who, accumulate_only ? "accumulate_only needs gsum" : "the step needs x_cur, x_orig and x_next");
     if (!accumulate_only && (!(eps >= 0.f) || !(eps_iter >= 0.f) || !(clip_min <= clip_max)))
-        return clf_fail(DG_E_INVALID, "dg_bpda_step: eps and eps_iter must be >= 0 and clip_min <= clip_max");
+        return clf_fail(DG_E_INVALID, "%s: eps and eps_iter must be >= 0 and clip_min <= clip_max", who);
     CLF_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     int rc = clf_kept_forward(h, rec, B, s);
@@ -139,8 +135,24 @@ int dg_bpda_step(dg_clf* h, const float* rec, const int32_t* labels, int B, cons
     clf_launch_ce_grad(h->acts[h->logit_layer], labels, h->bpda->seed, B, h->n_logits, s);
     float* g = nullptr;
     if ((rc = clf_seeded_backward(h, h->bpda->seed, B, s, &g))) return rc;
+    if (ball && !accumulate_only) return clf_launch_ball_step(g, gsum, x_cur, x_orig, x_next, B, h->pixels(), eps, eps_iter, clip_min, clip_max, s);
     return clf_launch_bpda_step(g, gsum, x_cur, x_orig, x_next, (long long)B * h->pixels(), h->pixels(), accumulate_only, eps, eps_iter,
                                 clip_min, clip_max, s);
+}
+
+extern "C" {
+
+int dg_bpda_step(dg_clf* h, const float* rec, const int32_t* labels, int B, const float* x_cur, const float* x_orig, float* gsum,
+                 int accumulate_only, float eps, float eps_iter, float clip_min, float clip_max, float* x_next, void* stream) {
+    return bpda_step_run("dg_bpda_step", false, h, rec, labels, B, x_cur, x_orig, gsum, accumulate_only, eps, eps_iter, clip_min, clip_max,
+                         x_next, stream);
+}
+
+int dg_bpda_step_ball(dg_clf* h, const float* rec, const int32_t* labels, int B, const float* x_cur, const float* x_orig, float* gsum,
+                      int accumulate_only, float eps, float eps_iter, int ord, float clip_min, float clip_max, float* x_next, void* stream) {
+    if (ord != 2) return clf_fail(DG_E_INVALID, "dg_bpda_step_ball: ord must be 2 (the L1 projection needs a sort), got %d", ord);
+    return bpda_step_run("dg_bpda_step_ball", true, h, rec, labels, B, x_cur, x_orig, gsum, accumulate_only, eps, eps_iter, clip_min, clip_max,
+                         x_next, stream);
 }
 
 int dg_bpda_track(const int32_t* preds, const int32_t* labels, int B, int k, const float* x_iter, float* x_best, int32_t* first_success,

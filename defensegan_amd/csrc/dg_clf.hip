@@ -544,4 +544,16 @@ int dg_fgsm(dg_clf* h, const float* x, const int32_t* labels, int B, float eps, 
     return DG_OK;
 }
 
+int dg_fgm(dg_clf* h, const float* x, const int32_t* labels, int B, float eps, int ord, float clip_min, float clip_max, float* x_adv,
+           void* stream) {
+    if (!h || !x || !x_adv || B <= 0) return clf_fail(DG_E_INVALID, "dg_fgm: bad argument");
+    if (ord != 1 && ord != 2) return clf_fail(DG_E_INVALID, "dg_fgm: ord must be 1 or 2 (ord = inf is dg_fgsm), got %d", ord);
+    CLF_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    float* g = nullptr;
+    int rc = clf_input_gradient(h, x, labels, B, &g, s);
+    if (rc) return rc;
+    return clf_launch_fgm_norm_step(x, g, x_adv, B, h->pixels(), ord, eps, clip_min, clip_max, s);        // dg_ball.hip
+}
+
 }  // extern "C"

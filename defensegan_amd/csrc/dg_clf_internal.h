@@ -1,6 +1,6 @@
-// The classifier handle as its six source files see it: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
-// dg_cw.hip (the Carlini-Wagner attack), dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation), dg_bpda.hip (the BPDA/EOT step) and dg_pgd.hip (PGD on the bare
-// classifier).  Everything here is internal to the library: plain C++
+// The classifier handle as its seven source files see it: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
+// dg_cw.hip (the Carlini-Wagner attack), dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation), dg_bpda.hip (the BPDA/EOT step), dg_pgd.hip (PGD on the bare
+// classifier) and dg_ball.hip (the per-image norms and steps of the L1 / L2 attacks).  Everything here is internal to the library: plain C++
 // under hidden visibility, nothing of it is exported.
 #pragma once
 
@@ -112,11 +112,32 @@ void jac_release(JacWork* w);        // dg_jacobian.hip
 void bpda_release(BpdaWork* w);      // dg_bpda.hip
 void pgd_release(PgdWork* w);        // dg_pgd.hip
 
+// ---- shared by the attack steps (dg_bpda.hip, dg_ball.hip) -------------------------------------------------------------------------
+// the final clip of every attack step: clip(v, lo, hi) with lo <= hi
+__device__ __forceinline__ float clf_clip(float v, float lo, float hi) {
+    v = v < lo ? lo : v;
+    return v > hi ? hi : v;
+}
+// whether float4 may be used on p (NULL counts as aligned: an absent operand)
+inline bool clf_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // ---- dg_bpda.hip ----------------------------------------------------------------------------------------------------------------
 // The projected sign step over `total` elements (rows of row_elems): accumulate_only: gsum += g; otherwise t = gsum + g (t = g when
 // gsum == NULL) and x_next = clip(x_orig + clamp(x_cur + eps_iter sign(t) - x_orig, -eps, eps), lo, hi).  float4 where row_elems is
 // a multiple of 4 and every pointer given is 16-byte aligned.
 int clf_launch_bpda_step(const float* g, float* gsum, const float* x_cur, const float* x_orig, float* x_next, long long total,
                          int row_elems, int accumulate_only, float eps, float eps_iter, float lo, float hi, hipStream_t s);
+
+// ---- dg_ball.hip ----------------------------------------------------------------------------------------------------------------
+// One workgroup per image; float4 where row_elems is a multiple of 4 and every pointer given is 16-byte aligned.  ord is 1 or 2.
+// out[b] = the ord-norm of row b of v - w (of v when w == NULL)
+int clf_launch_row_norms(const float* v, const float* w, int B, long long row_elems, int ord, float* out, hipStream_t s);
+// out = clip(x + eps * g / max(1e-12, ||g||_ord), lo, hi), the norm per image
+int clf_launch_fgm_norm_step(const float* x, const float* g, float* out, int B, int row_elems, int ord, float eps, float lo, float hi,
+                             hipStream_t s);
+// The L2 step: t = gsum + g (t = g when gsum == NULL), d = (x_cur + eps_iter * t / max(1e-12, ||t||)) - x_orig,
+// x_next = clip(x_orig + d * min(1, eps / max(1e-12, ||d||)), lo, hi); the norms per image.
+int clf_launch_ball_step(const float* g, const float* gsum, const float* x_cur, const float* x_orig, float* x_next, int B, int row_elems,
+                         float eps, float eps_iter, float lo, float hi, hipStream_t s);
 
 #pragma GCC visibility pop

@@ -10,7 +10,8 @@
 // is the first arg-max of the logits that iteration j's forward keeps for its backward (pgd_track_kernel); only the last iterate
 // needs one trailing forward.  A call is nb_iter + 1 forwards and nb_iter backwards through clf_kept_forward, clf_launch_ce_grad and
 // clf_seeded_backward (dg_clf_internal.h: the launchers dg_clf_input_gradient and dg_bpda_step use, in their order) and
-// clf_launch_bpda_step with gsum == NULL.
+// clf_launch_bpda_step with gsum == NULL.  dg_pgd_ball is the same call with the L2 step of dg_ball.hip (clf_launch_ball_step) in
+// the projected sign step's place (still one launch per step); the chain and the tracking are shared.
 //
 // Every output element is one thread's (or one wave's) fixed-order arithmetic on its own image: the result does not depend on how
 // many images share a call.  No atomics, no host synchronisation, no graph capture.  gfx950 only.
@@ -84,17 +85,14 @@ int pgd_track(const dg_clf* h, const int32_t* labels, int B, int k, const float*
     return DG_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dg_pgd(dg_clf* h, const float* x, const float* x_start, const int32_t* labels, int B, float eps, float eps_iter, int nb_iter,
-           float clip_min, float clip_max, float* x_adv, int32_t* first_success, void* stream) {
-    if (nb_iter < 1) return clf_fail(DG_E_INVALID, "dg_pgd: nb_iter must be >= 1, got %d", nb_iter);
-    if (!(eps >= 0.f) || !(eps_iter >= 0.f)) return clf_fail(DG_E_INVALID, "dg_pgd: eps and eps_iter must be >= 0");
-    if (!(clip_min <= clip_max)) return clf_fail(DG_E_INVALID, "dg_pgd: clip_min must not exceed clip_max");
-    if (!h || !x || !x_start || !labels || !x_adv || !first_success || B <= 0) return clf_fail(DG_E_INVALID, "dg_pgd: bad argument");
-    if (x_adv == x || x_adv == x_start) return clf_fail(DG_E_INVALID, "dg_pgd: x_adv must not be x or x_start");
+// dg_pgd and dg_pgd_ball: the same chain, the step either the projected sign step or (ball) the L2 step of dg_ball.hip.
+int pgd_run(const char* who, bool ball, dg_clf* h, const float* x, const float* x_start, const int32_t* labels, int B, float eps, float eps_iter,
+            int nb_iter, float clip_min, float clip_max, float* x_adv, int32_t* first_success, void* stream) {
+    if (nb_iter < 1) return clf_fail(DG_E_INVALID, "%s: nb_iter must be >= 1, got %d", who, nb_iter);
+    if (!(eps >= 0.f) || !(eps_iter >= 0.f)) return clf_fail(DG_E_INVALID, "%s: eps and eps_iter must be >= 0", who);
+    if (!(clip_min <= clip_max)) return clf_fail(DG_E_INVALID, "%s: clip_min must not exceed clip_max", who);
+    if (!h || !x || !x_start || !labels || !x_adv || !first_success || B <= 0) return clf_fail(DG_E_INVALID, "%s: bad argument", who);
+    if (x_adv == x || x_adv == x_start) return clf_fail(DG_E_INVALID, "%s: x_adv must not be x or x_start", who);
     CLF_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (!h->pgd) h->pgd = new PgdWork();
@@ -113,11 +111,28 @@ int dg_pgd(dg_clf* h, const float* x, const float* x_start, const int32_t* label
         float* g = nullptr;
         if ((rc = clf_seeded_backward(h, w->seed, B, s, &g))) return rc;
         float* next = w->iter[k & 1];
-        if ((rc = clf_launch_bpda_step(g, nullptr, cur, x, next, (long long)B * P, P, 0, eps, eps_iter, clip_min, clip_max, s))) return rc;
+        rc = ball ? clf_launch_ball_step(g, nullptr, cur, x, next, B, P, eps, eps_iter, clip_min, clip_max, s)
+                  : clf_launch_bpda_step(g, nullptr, cur, x, next, (long long)B * P, P, 0, eps, eps_iter, clip_min, clip_max, s);
+        if (rc) return rc;
         cur = next;
     }
     if ((rc = clf_kept_forward(h, cur, B, s))) return rc;                                   // the last iterate's trailing forward
     return pgd_track(h, labels, B, nb_iter, cur, x_adv, first_success, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dg_pgd(dg_clf* h, const float* x, const float* x_start, const int32_t* labels, int B, float eps, float eps_iter, int nb_iter,
+           float clip_min, float clip_max, float* x_adv, int32_t* first_success, void* stream) {
+    return pgd_run("dg_pgd", false, h, x, x_start, labels, B, eps, eps_iter, nb_iter, clip_min, clip_max, x_adv, first_success, stream);
+}
+
+int dg_pgd_ball(dg_clf* h, const float* x, const float* x_start, const int32_t* labels, int B, float eps, float eps_iter, int nb_iter,
+                int ord, float clip_min, float clip_max, float* x_adv, int32_t* first_success, void* stream) {
+    if (ord != 2) return clf_fail(DG_E_INVALID, "dg_pgd_ball: ord must be 2 (the L1 projection needs a sort), got %d", ord);
+    return pgd_run("dg_pgd_ball", true, h, x, x_start, labels, B, eps, eps_iter, nb_iter, clip_min, clip_max, x_adv, first_success, stream);
 }
 
 }  // extern "C"

@@ -520,10 +520,50 @@ MLP.class_gradient = _mlp_class_gradient
 MLP.jacobian = _mlp_jacobian
 
 
+_L1_ITERATIVE_NOTE = ("ord = 1 is not implemented for the iterative attacks: the projection onto an L1 ball needs a sort per image; "
+                      "ord = np.inf and ord = 2 are")
+
+
+def _attack_ord(ord, allowed, who):
+    """``ord`` as np.inf, 1 or 2 ('inf' and float('inf') are np.inf); anything else, or a value not in ``allowed``, is refused."""
+    if isinstance(ord, str):
+        ord = {"inf": np.inf, "1": 1, "2": 2}.get(ord.lower(), ord)
+    if not isinstance(ord, str) and ord in (np.inf, 1, 2):
+        ord = np.inf if ord == np.inf else int(ord)
+        if ord in allowed:
+            return ord
+        if ord == 1:
+            raise NotImplementedError("%s: %s" % (who, _L1_ITERATIVE_NOTE))
+    raise ValueError("%s: ord must be one of %s, got %r" % (who, ", ".join("np.inf" if a == np.inf else str(a) for a in allowed), ord))
+
+
+def ball_project_noise(noise, eps):
+    """The ``rand_init`` draw for ord = 2: ``noise`` [n, P] (``bpda_rand_noise``, uniform in the L-infinity cube) scaled per image by
+    ``min(1, eps / max(1e-12, ||noise||_2))`` onto the L2 ball, in float32 on the host (the norm in float64, rounded once)."""
+    noise = np.asarray(noise, np.float32)
+    norm = np.sqrt(np.square(noise.astype(np.float64)).sum(axis=1))
+    scale = np.minimum(1.0, float(eps) / np.maximum(1e-12, norm)).astype(np.float32)
+    return noise * scale[:, None]
+
+
+def _row_norms(v, w, ord=2):
+    """[n] float32 on the device: the per-image ``ord``-norm of ``v - w`` (of ``v`` when ``w`` is None), ``dg_row_norms``; device
+    tensors [n, ...] on torch's current stream, not waited for."""
+    import torch
+    n = int(v.shape[0])
+    out = torch.empty(n, dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        _native.check(_native.load().dg_row_norms(v.data_ptr(), w.data_ptr() if w is not None else None, n, int(v.numel() // n), int(ord),
+                                                  out.data_ptr(), torch.cuda.current_stream(v.device).cuda_stream))
+    return out
+
+
 class FastGradientMethod(object):
-    """The cleverhans attack object the reference instantiates (whitebox.py:198-200, blackbox.py:530-534), ord = inf only:
+    """The cleverhans attack object the reference instantiates (whitebox.py:198-200, blackbox.py:530-534) with ord = inf:
     ``adv = clip(x + eps * sign(grad_x CE(model(x), y)), clip_min, clip_max)``; without ``y`` the model's own prediction is
-    the label (cleverhans' default).  ``sess`` / ``back`` are accepted for signature compatibility and ignored.
+    the label (cleverhans' default).  ``ord`` 1 and 2 are cleverhans' as well, the norm per image over its H W C elements
+    (``dg_fgm``): ``adv = clip(x + eps * g / max(1e-12, sum|g|), ...)`` and ``adv = clip(x + eps * g / max(1e-12, sqrt(sum g^2)), ...)``;
+    a zero gradient gives a zero step.  ``sess`` / ``back`` are accepted for signature compatibility and ignored.
 
     White-box use on a DEFENDED model (whitebox.py:185-200 attaches the reconstruction layer first, then builds the attack
     on that model): the gradient through the projection is identically zero in the reference, so ``generate`` returns
@@ -534,8 +574,7 @@ class FastGradientMethod(object):
 
     def generate(self, x, eps=0.3, ord=np.inf, y=None, clip_min=None, clip_max=None, **kwargs):
         import torch
-        if ord not in (np.inf, "inf", float("inf")):
-            raise NotImplementedError("only ord = inf (the reference's setting) is implemented")
+        ord = _attack_ord(ord, (np.inf, 1, 2), "FastGradientMethod")
         m = self.model
         m._ensure()
         was_numpy = isinstance(x, np.ndarray)
@@ -557,8 +596,12 @@ class FastGradientMethod(object):
         out = torch.empty_like(t)
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            _native.check(_native.load().dg_fgsm(m._handle, t.data_ptr(), lab.data_ptr() if lab is not None else None,
-                                                 int(t.shape[0]), float(eps), lo, hi, out.data_ptr(), stream))
+            if ord == np.inf:
+                _native.check(_native.load().dg_fgsm(m._handle, t.data_ptr(), lab.data_ptr() if lab is not None else None,
+                                                     int(t.shape[0]), float(eps), lo, hi, out.data_ptr(), stream))
+            else:
+                _native.check(_native.load().dg_fgm(m._handle, t.data_ptr(), lab.data_ptr() if lab is not None else None,
+                                                    int(t.shape[0]), float(eps), int(ord), lo, hi, out.data_ptr(), stream))
         return out.cpu().numpy() if was_numpy else out
 
 
@@ -696,7 +739,7 @@ def bpda_seed_schedule(seed: int, nb_iter: int, eot_samples: int):
 
 
 class BpdaDeviceOps(object):
-    """The four device operations ``BPDA.generate`` is made of, on tensors of the classifier's device and torch's current stream;
+    """The device operations ``BPDA.generate`` is made of (``step_ball`` and ``dist`` only with ``ord = 2``), on tensors of the classifier's device and torch's current stream;
     none of them waits for the device.  (``BPDA`` takes any object with these methods and a ``device``: the tests drive the loop
     with a recording stand-in.)"""
 
@@ -727,6 +770,20 @@ class BpdaDeviceOps(object):
                 1 if accumulate_only else 0, float(eps), float(eps_iter), float(clip_min), float(clip_max), ptr(x_next),
                 torch.cuda.current_stream(self.device).cuda_stream))
 
+    def step_ball(self, rec, labels, x_cur, x_orig, gsum, accumulate_only, eps, eps_iter, ord, clip_min, clip_max, x_next):
+        """dg_bpda_step_ball: ``step`` with the L2 step (``ord`` = 2) in the projected sign step's place."""
+        import torch
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().dg_bpda_step_ball(
+                self.model._handle, rec.data_ptr(), labels.data_ptr(), int(rec.shape[0]), ptr(x_cur), ptr(x_orig), ptr(gsum),
+                1 if accumulate_only else 0, float(eps), float(eps_iter), int(ord), float(clip_min), float(clip_max), ptr(x_next),
+                torch.cuda.current_stream(self.device).cuda_stream))
+
+    def dist(self, x_adv, x_orig):
+        """dg_row_norms: [n] float32, the per-image L2 distance of ``x_adv`` from ``x_orig``."""
+        return _row_norms(x_adv, x_orig, 2)
+
     def track(self, preds, labels, k, x_iter, x_best, first_success):
         """dg_bpda_track: images still without a success take iterate k as their best, and k as their first success where
         ``preds != labels``."""
@@ -754,6 +811,12 @@ class BPDA(object):
     per image the first successful iterate, or the last iterate; ``return_info=True`` adds ``first_success`` [n] int32 (the
     iterate's index in 1 .. nb_iter, or -1).
 
+    ``ord = 2`` (default np.inf) bounds the perturbation in L2 instead, every norm per image over its H W C elements:
+    ``u = g_k / max(1e-12, ||g_k||)``, ``d = (x_k + eps_iter u) - x``, ``x_{k+1} = clip(x + d min(1, eps / max(1e-12, ||d||)), ...)``
+    (``dg_bpda_step_ball``; a zero gradient gives a zero step); ``rand_init`` then draws ``ball_project_noise(bpda_rand_noise(...))``,
+    the same draw scaled onto the L2 ball on the host; and ``return_info=True`` returns a third value, ``dist`` [n] float32, the
+    distance ``||x_adv - x||_2`` (``dg_row_norms``).  ``ord = 1`` raises NotImplementedError: its projection needs a sort.
+
     ``x`` NumPy or a device tensor [n, H, W, C] in generator range (NumPy in gives NumPy out; a tensor gives tensors on the
     caller's current stream, not waited for); ``y`` class indices or one-hot rows, required.  ``seed`` defaults to
     BPDA_DEFAULT_SEED.  The latents of image i are rows ``i * rec_rr + r`` of the seeded stream and every classifier output is
@@ -770,9 +833,10 @@ class BPDA(object):
         self._ops = ops
 
     def generate(self, x, y, eps=0.3, eps_iter=0.05, nb_iter=10, eot_samples=1, clip_min=None, clip_max=None, rand_init=False,
-                 seed=None, x_init=None, batch_size=None, return_info=False):
+                 seed=None, x_init=None, batch_size=None, return_info=False, ord=np.inf):
         import torch
         from . import gan_defense
+        ord = _attack_ord(ord, (np.inf, 2), "BPDA")
         m = self.model
         rl = m.rec_layer
         if rl is None:
@@ -813,7 +877,8 @@ class BPDA(object):
             if tuple(x_cur.shape) != tuple(t.shape):
                 raise ValueError("x_init must have x's shape")
         elif rand_init:
-            noise = torch.from_numpy(bpda_rand_noise(n, P, eps, seed)).to(dev).view_as(t)
+            noise = bpda_rand_noise(n, P, eps, seed)
+            noise = torch.from_numpy(noise if ord == np.inf else ball_project_noise(noise, eps)).to(dev).view_as(t)
             x_cur = torch.clamp(t + noise, lo, hi)
         else:
             x_cur = torch.clamp(t, lo, hi)
@@ -836,15 +901,19 @@ class BPDA(object):
                     rec = ops.project(x_cur[a:b], seeds[k][s], a * R)
                     if s == 0 and k > 0:                           # rec_{k,0} is the defended view of iterate k
                         ops.track(ops.predict(rec), lab[a:b], k, x_cur[a:b], x_best[a:b], first_success[a:b])
-                    ops.step(rec, lab[a:b], x_cur[a:b], t[a:b], gsum[a:b] if gsum is not None else None, s < mm - 1, eps, eps_iter,
-                             lo, hi, x_next[a:b])
+                    gs = gsum[a:b] if gsum is not None else None
+                    if ord == np.inf:
+                        ops.step(rec, lab[a:b], x_cur[a:b], t[a:b], gs, s < mm - 1, eps, eps_iter, lo, hi, x_next[a:b])
+                    else:
+                        ops.step_ball(rec, lab[a:b], x_cur[a:b], t[a:b], gs, s < mm - 1, eps, eps_iter, ord, lo, hi, x_next[a:b])
             x_cur, x_next = x_next, x_cur
         for a, b in cuts:
             rec = ops.project(x_cur[a:b], final_seed, a * R)
             ops.track(ops.predict(rec), lab[a:b], nb_iter, x_cur[a:b], x_best[a:b], first_success[a:b])
+        info = (first_success,) if ord == np.inf or not return_info else (first_success, ops.dist(x_best, t))
         if was_numpy:
-            x_best, first_success = x_best.cpu().numpy(), first_success.cpu().numpy()
-        return (x_best, first_success) if return_info else x_best
+            x_best, info = x_best.cpu().numpy(), tuple(v.cpu().numpy() for v in info)
+        return (x_best,) + info if return_info else x_best
 
 
 class ProjectedGradientDescent(object):
@@ -860,6 +929,11 @@ class ProjectedGradientDescent(object):
     iterate's index in 1 .. nb_iter, or -1).  The prediction is read off the logits the next iteration's forward keeps:
     ``nb_iter + 1`` forwards and ``nb_iter`` backwards in all.
 
+    ``ord = 2`` (default np.inf) is the L2 attack, as ``BPDA``'s: the step ``u = g_k / max(1e-12, ||g_k||)``, ``d = (x_k + eps_iter u) - x``,
+    ``x_{k+1} = clip(x + d min(1, eps / max(1e-12, ||d||)), ...)`` with every norm per image (``dg_pgd_ball``, still one device call);
+    ``rand_init`` draws ``ball_project_noise(bpda_rand_noise(...))`` on the host; ``return_info=True`` returns a third value, ``dist`` [n]
+    float32 = ``||x_adv - x||_2`` (``dg_row_norms``).  ``ord = 1`` raises NotImplementedError: its projection needs a sort.
+
     ``x`` NumPy or a device tensor [n, H, W, C] (NumPy in gives NumPy out; a tensor gives tensors on the caller's current stream,
     not waited for); ``y`` class indices or one-hot rows, required; a class index outside [0, nb_classes) gives that image a zero
     gradient (training's policy): it stays at x_0.  ``seed`` (default BPDA_DEFAULT_SEED) keys the ``rand_init`` draw, by the
@@ -872,8 +946,9 @@ class ProjectedGradientDescent(object):
         self.model = model
 
     def generate(self, x, y, eps=0.3, eps_iter=0.05, nb_iter=10, clip_min=None, clip_max=None, rand_init=False, seed=None, x_init=None,
-                 batch_size=None, return_info=False):
+                 batch_size=None, return_info=False, ord=np.inf):
         import torch
+        ord = _attack_ord(ord, (np.inf, 2), "ProjectedGradientDescent")
         m = self.model
         if m.rec_layer is not None:
             raise ValueError("ProjectedGradientDescent attacks a bare classifier; this model has the Defense-GAN projection attached "
@@ -913,7 +988,8 @@ class ProjectedGradientDescent(object):
             if tuple(x0.shape) != tuple(t.shape):
                 raise ValueError("x_init must have x's shape")
         elif rand_init:
-            x0 = torch.clamp(t + torch.from_numpy(bpda_rand_noise(n, P, eps, seed)).to(dev).view_as(t), lo, hi)
+            noise = bpda_rand_noise(n, P, eps, seed)
+            x0 = torch.clamp(t + torch.from_numpy(noise if ord == np.inf else ball_project_noise(noise, eps)).to(dev).view_as(t), lo, hi)
         else:
             x0 = torch.clamp(t, lo, hi)
         x_adv = torch.empty_like(t)
@@ -923,12 +999,18 @@ class ProjectedGradientDescent(object):
         with torch.cuda.device(dev):
             for a in range(0, n, bs):
                 b = min(n, a + bs)
-                _native.check(_native.load().dg_pgd(m._handle, t[a:b].data_ptr(), x0[a:b].data_ptr(), lab[a:b].data_ptr(), b - a, float(eps),
-                                                    float(eps_iter), nb_iter, lo, hi, x_adv[a:b].data_ptr(), first_success[a:b].data_ptr(),
-                                                    stream))
+                if ord == np.inf:
+                    _native.check(_native.load().dg_pgd(m._handle, t[a:b].data_ptr(), x0[a:b].data_ptr(), lab[a:b].data_ptr(), b - a, float(eps),
+                                                        float(eps_iter), nb_iter, lo, hi, x_adv[a:b].data_ptr(), first_success[a:b].data_ptr(),
+                                                        stream))
+                else:
+                    _native.check(_native.load().dg_pgd_ball(m._handle, t[a:b].data_ptr(), x0[a:b].data_ptr(), lab[a:b].data_ptr(), b - a,
+                                                             float(eps), float(eps_iter), nb_iter, ord, lo, hi, x_adv[a:b].data_ptr(),
+                                                             first_success[a:b].data_ptr(), stream))
+        info = (first_success,) if ord == np.inf or not return_info else (first_success, _row_norms(x_adv, t, 2))
         if was_numpy:
-            x_adv, first_success = x_adv.cpu().numpy(), first_success.cpu().numpy()
-        return (x_adv, first_success) if return_info else x_adv
+            x_adv, info = x_adv.cpu().numpy(), tuple(v.cpu().numpy() for v in info)
+        return (x_adv,) + info if return_info else x_adv
 
 
 def rand_fgsm_prestep(test_images, eps: float, alpha: float, min_val: float = 0.0, max_val: float = 1.0, rng=None):

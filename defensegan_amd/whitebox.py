@@ -47,6 +47,15 @@ def attack_kind(attack_type):
     raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, pgd (defense_type none / adv_tr) or bpda (defense_gan)" % (attack_type,))
 
 
+def attack_ord_value(attack_ord, kind=None):
+    """``attack_ord`` (np.inf, 1, 2 or their names 'inf', '1', '2') as np.inf or an int, checked against the attack ``kind``: fgsm
+    takes 1 and 2 (``FastGradientMethod``'s ord), pgd and bpda take 2 (1 is NotImplementedError: the L1 projection needs a sort), cw
+    is an L2 attack already and takes none."""
+    who = "attack_ord" if kind is None else "attack_ord with attack_type %s" % kind
+    allowed = {"fgsm": (np.inf, 1, 2), "pgd": (np.inf, 2), "bpda": (np.inf, 2), "cw": (np.inf,)}.get(kind, (np.inf, 1, 2))
+    return network_builder._attack_ord(attack_ord, allowed, who)
+
+
 def _attack_params(kind, attack_params):
     """The overrides ``attack_params`` holds for this attack: eps_iter / nb_iter (pgd, bpda), eot_samples (bpda), any
     CarliniWagnerL2 parameter (cw).  Values of None and the iterative attacks' keys given to another attack are left out."""
@@ -62,7 +71,8 @@ def _attack_params(kind, attack_params):
 
 def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate=0.001, nb_epochs=10, eps=0.3, alpha=0.05,
              online_training=False, train_on_recs=False, test_on_dev=True, attack_type="fgsm", defense_type="none", num_tests=-1,
-             num_train=-1, fgsm_eps_tr=0.15, same_init=False, recs=None, attack_params=None, seed=SEED, init_seed=0, phases=None):
+             num_train=-1, fgsm_eps_tr=0.15, same_init=False, recs=None, attack_params=None, seed=SEED, init_seed=0, phases=None,
+             attack_ord=np.inf):
     """whitebox.py:56-233.  ``gan``: a DefenseGANBase with its generator loaded, or None (``defense_type`` 'none' and 'adv_tr' need
     none); ``model``: the classifier's MLP (initialised with the reference's initialisers from ``init_seed`` when its weights are not
     set); ``data`` = (train_images, train_labels, test_images, test_labels), the ORIGINAL images in generator range, labels one-hot
@@ -81,7 +91,9 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
       pgd               ProjectedGradientDescent on the true labels: 'none' and 'adv_tr' only
       bpda              BPDA on the true labels: 'defense_gan' only
     ``attack_params`` overrides ``eps_iter`` (0.05), ``nb_iter`` (10), ``eot_samples`` (1) of pgd / bpda and any CarliniWagnerL2
-    parameter.  pgd with 'defense_gan' or bpda without it is a ValueError.
+    parameter.  pgd with 'defense_gan' or bpda without it is a ValueError.  ``attack_ord`` (default np.inf): 2 runs pgd / bpda in an
+    L2 ball of radius ``eps`` (their ``ord``), 1 or 2 runs fgsm / rand_fgsm as FGM with that norm; 1 with pgd / bpda is
+    NotImplementedError, any value but np.inf with cw a ValueError.
 
     ``defense_gan``: the reconstruction layer is attached after training (``same_init``: with one sigma = 1 draw of
     [batch_size * rec_rr, latent_dim] as every batch's z0), the attack is built on that model, and the accuracy comes from
@@ -111,6 +123,9 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
         if kind[0] == "bpda" and same_init:
             raise ValueError("attack_type bpda draws fresh latents for every projection: not with same_init")
         extra = _attack_params(kind[0], attack_params)
+        attack_ord = attack_ord_value(attack_ord, kind[0])
+        if attack_ord != np.inf and kind[0] in ("pgd", "bpda"):
+            extra["ord"] = attack_ord
     if online_training:
         raise NotImplementedError("online_training (training through the Defense-GAN projection) is not implemented; the reference's "
                                   "whitebox() takes the flag and never trains through the projection either (it only enters the "
@@ -169,7 +184,7 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
     with _Phase(phases, "attack", dev):
         if kind == "fgsm":
             attack = network_builder.FastGradientMethod(model)
-            par = {"eps": eps, "ord": np.inf, "clip_min": min_val, "clip_max": 1.0}
+            par = {"eps": eps, "ord": attack_ord, "clip_min": min_val, "clip_max": 1.0}
             x_adv = utils_tf.batch_eval(lambda xb: attack.generate(xb, **par), test_adv_from, batch_size)
         elif kind == "cw":
             attack = attack or network_builder.CarliniWagnerL2(model)
@@ -217,7 +232,8 @@ def get_results_dir_filename(flags, gan):
     if flags.num_train > -1:
         result_file_name = "numtrain={}_".format(flags.num_train) + result_file_name
     result_file_name = "model={}_".format(flags.model) + result_file_name
-    result_file_name += "attack={}.txt".format(flags.attack_type)
+    attack_ord = attack_ord_value(getattr(flags, "attack_ord", np.inf))
+    result_file_name += "attack={}{}.txt".format(flags.attack_type, "" if attack_ord == np.inf else "_ord={}".format(attack_ord))
     return results_dir, result_file_name
 
 
@@ -263,6 +279,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eps_iter", type=float, default=None, help="pgd / bpda step size (default 0.05)")
     ap.add_argument("--nb_iter", type=int, default=None, help="pgd / bpda iterations (default 10)")
     ap.add_argument("--eot_samples", type=int, default=None, help="bpda: projections the gradient is summed over per iteration (default 1)")
+    ap.add_argument("--attack_ord", default="inf", choices=["inf", "1", "2"],
+                    help="norm of the attack's ball: pgd / bpda take inf or 2, fgsm / rand_fgsm inf, 1 or 2 (default inf)")
     ap.add_argument("--seed", type=int, default=SEED, help="seed of the Dropout masks and the latent draws")
     ap.add_argument("--init_seed", type=int, default=0, help="seed of the classifier's initial weights")
     return ap
@@ -309,7 +327,7 @@ def main(argv=None) -> int:
                           defense_type=args.defense_type, num_tests=args.num_tests, num_train=args.num_train,
                           fgsm_eps_tr=args.fgsm_eps_tr, same_init=args.same_init, recs=recs,
                           attack_params={"eps_iter": args.eps_iter, "nb_iter": args.nb_iter, "eot_samples": args.eot_samples},
-                          seed=args.seed, init_seed=args.init_seed)
+                          seed=args.seed, init_seed=args.init_seed, attack_ord=args.attack_ord)
     write_results(path, accuracies)
     return 0
 

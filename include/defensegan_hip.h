@@ -416,6 +416,28 @@ int dg_pgd(dg_clf* h, const float* x, const float* x_start, const int32_t* label
            float clip_min, float clip_max, float* x_adv, int32_t* first_success, void* stream);
 
 /*
+ * The L1 / L2 forms of the attacks above (defensegan_amd/csrc/dg_ball.hip's header comment and DESIGN.md section 7, "L2 balls").
+ * Every norm is per image, over its in_h * in_w * in_c elements, one fixed-order float32 sum computed by the image's own workgroup
+ * inside the call: no atomics, no host synchronisation, and no dependence on how many images share a call.  tiny = 1e-12 guards
+ * every division: a zero gradient gives a zero step, never a NaN.  Device pointers; asynchronous on `stream`.
+ */
+/* cleverhans' fgm for ord 1 and 2 (ord = inf is dg_fgsm): g = dg_clf_input_gradient's bits (labels [B] int32, or NULL for the model's
+ * own first arg-max), x_adv = clip(x + eps * g / max(tiny, n(g)), clip_min, clip_max) with n = sum |g| (ord 1) or sqrt(sum g^2) (ord 2). */
+int dg_fgm(dg_clf* h, const float* x, const int32_t* labels, int B, float eps, int ord, float clip_min, float clip_max, float* x_adv,
+           void* stream);
+/* dg_bpda_step with the L2 step (ord must be 2; the L1 projection needs a sort and is not implemented): accumulate_only != 0 is
+ * dg_bpda_step's gsum += g; otherwise t = gsum + g (t = g when gsum == NULL), u = t / max(tiny, ||t||), d = (x_cur + eps_iter * u) - x_orig,
+ * x_next = clip(x_orig + d * min(1, eps / max(tiny, ||d||)), clip_min, clip_max). */
+int dg_bpda_step_ball(dg_clf* h, const float* rec, const int32_t* labels, int B, const float* x_cur, const float* x_orig, float* gsum,
+                      int accumulate_only, float eps, float eps_iter, int ord, float clip_min, float clip_max, float* x_next, void* stream);
+/* dg_pgd with that L2 step in the projected sign step's place (ord must be 2): the same gradients, tracking, outputs and checks. */
+int dg_pgd_ball(dg_clf* h, const float* x, const float* x_start, const int32_t* labels, int B, float eps, float eps_iter, int nb_iter,
+                int ord, float clip_min, float clip_max, float* x_adv, int32_t* first_success, void* stream);
+/* out [B] = per row of row_elems floats the ord-norm (1: sum |.|, 2: sqrt(sum .^2)) of v - w, or of v when w == NULL.  Runs on the
+ * current device. */
+int dg_row_norms(const float* v, const float* w, int B, int64_t row_elems, int ord, float* out, void* stream);
+
+/*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
  * (no collective on the data path) and ONE all_gather assembles the evaluation message -- per rank `count` int32 words, e.g.
  * [n | labels (cap) | preds (cap) | diffs (cap, float32 bits)] as defensegan_amd/gan_defense.py:model_eval_gan_sharded builds it
