@@ -4,6 +4,16 @@ asymmetric SAME padding, the input gradient from autograd, the loss gradient fro
 
     out = cw_l2(layers_of(model), params, x, labels, targeted=False, batch_size=..., ...)
     out["x_adv"], out["best_l2"], out["best_class"], out["const"], out["abort_iters"]   # abort_iters[outer][chunk]: iteration or None
+
+With ``trace=True`` the result also holds out["trace"]: how close every decision of the run came to flipping, in float64 (NaN
+where an iteration did not take the decision: after a stop, and the best tracking of the stopping iteration itself).
+
+    success_margin [N, outer, iteration]   |Z'_t - max_{k != t} Z'_k|: the top entry of Z' against the runner-up when the label is
+                                           on top, against the label's entry when it is not (Z' = Z with the label moved by kappa)
+    arg_margin     [N, outer, iteration]   |arg|, arg = real - oth + kappa (targeted: oth - real + kappa), whose sign gates the seed
+    check_margin   [outer][chunk]          one |L - 0.9999 prev| / prev per check the chunk made
+    step_success   [N, outer] bool         the outer step ended in success (what the constant update saw)
+    max_logit      [N]                     the largest |Z| the run saw
 """
 import numpy as np
 import torch
@@ -140,6 +150,50 @@ def const_update(bestscore, t, const, lower, upper, targeted):
     return const, lower, upper
 
 
+def success_margin(Z, t, confidence, targeted):
+    """|Z'_t - max_{k != t} Z'_k| per image: how far the success decision on Z' is from flipping."""
+    Zp = Z.clone()
+    idx = torch.arange(len(Z))
+    tt = torch.as_tensor(t)
+    Zp[idx, tt] += -confidence if targeted else confidence
+    own = Zp[idx, tt].clone()
+    Zp[idx, tt] = -float("inf")
+    return (own - Zp.max(1).values).abs().numpy()
+
+
+def arg_margin(Z, t, confidence, targeted):
+    """|arg| per image, arg being the hinge's argument (its sign decides whether loss1 has a gradient at all)."""
+    idx = torch.arange(len(Z))
+    tt = torch.as_tensor(t)
+    real = Z[idx, tt]
+    o = Z.clone()
+    o[idx, tt] = -10000.0
+    oth = o.max(1).values
+    return ((oth - real + confidence) if targeted else (real - oth + confidence)).abs().numpy()
+
+
+# The four places of the setup and the loop a mutated reference patches (tests/test_cw_cpu.py); cw_l2 looks them up at call time.
+def to_tanh_space(xc, lo, hi):
+    """timg: the image clipped to [lo, hi], scaled to (-1, 1) * 0.999999, through atanh."""
+    u = torch.clamp((xc - lo) / (hi - lo), 0, 1)
+    return torch.atanh((u * 2 - 1) * 0.999999)
+
+
+def own_label(Z):
+    """The label of a call without y / y_target: the model's own FIRST argmax (numpy's argmax takes the first of a tie)."""
+    return np.argmax(Z, axis=1)
+
+
+def rearm(prev, stopped):
+    """The chunk's abort state at the start of an outer step: (prev, the iteration that stopped it), whatever the last step left."""
+    return 1e6, None
+
+
+def step_bestscore(bestscore, stopped):
+    """The bestscore the constant update sees after an outer step that stopped at ``stopped`` (None: it ran to the end)."""
+    return bestscore
+
+
 def _success(Z, t, confidence, targeted):
     Zp = Z.clone()
     idx = torch.arange(len(Z))
@@ -149,13 +203,13 @@ def _success(Z, t, confidence, targeted):
 
 
 def cw_l2(layers, params, x, labels=None, targeted=False, batch_size=1, confidence=0.0, learning_rate=5e-3, binary_search_steps=5,
-          max_iterations=1000, abort_early=True, initial_const=1e-2, clip_min=0.0, clip_max=1.0):
+          max_iterations=1000, abort_early=True, initial_const=1e-2, clip_min=0.0, clip_max=1.0, trace=False):
     x = torch.as_tensor(np.asarray(x, np.float64))
     N = len(x)
     lo, hi = float(clip_min), float(clip_max)
     if labels is None:
         with torch.no_grad():
-            t_all = logits(layers, params, x).argmax(1).numpy()
+            t_all = own_label(logits(layers, params, x).numpy())
     else:
         t_all = np.asarray(labels)
         if t_all.ndim > 1:
@@ -167,13 +221,17 @@ def cw_l2(layers, params, x, labels=None, targeted=False, batch_size=1, confiden
     o_bestscore = np.full(N, -1, np.int64)
     const_all = np.full(N, float(initial_const))
     abort_iters = [[None] * ((N + batch_size - 1) // batch_size) for _ in range(binary_search_steps)]
+    tr = {"success_margin": np.full((N, binary_search_steps, max_iterations), np.nan),
+          "arg_margin": np.full((N, binary_search_steps, max_iterations), np.nan),
+          "check_margin": [[[] for _ in abort_iters[0]] for _ in range(binary_search_steps)],
+          "step_success": np.zeros((N, binary_search_steps), bool), "max_logit": np.zeros(N)}
     for ci, s in enumerate(range(0, N, batch_size)):
         sl = slice(s, min(s + batch_size, N))
         xc, t = x[sl], t_all[sl]
-        u = torch.clamp((xc - lo) / (hi - lo), 0, 1)
-        timg = torch.atanh((u * 2 - 1) * 0.999999)
+        timg = to_tanh_space(xc, lo, hi)
         other = to_img(torch.tanh(timg), lo, hi)
         n = len(xc)
+        prev, stopped = 1e6, None
         lower, upper, const = np.zeros(n), np.full(n, 1e10), np.full(n, float(initial_const))
         for outer in range(binary_search_steps):
             bestl2, bestscore = np.full(n, 1e10), np.full(n, -1, np.int64)
@@ -181,16 +239,21 @@ def cw_l2(layers, params, x, labels=None, targeted=False, batch_size=1, confiden
                 const = upper.copy()
             w = torch.zeros_like(xc)
             m, v = torch.zeros_like(xc), torch.zeros_like(xc)
-            prev = 1e6
-            for i in range(max_iterations):
+            prev, stopped = rearm(prev, stopped)
+            abort_iters[outer][ci] = stopped
+            for i in range(max_iterations if stopped is None else 0):
                 newimg, l2, Z, loss1, g = step_values(layers, params, w, timg, other, t, const, confidence, targeted, lo, hi)
                 w, m, v = adam_step(w, m, v, g, learning_rate, i + 1)
+                tr["arg_margin"][sl, outer, i] = arg_margin(Z, t, confidence, targeted)
+                tr["max_logit"][sl] = np.maximum(tr["max_logit"][sl], Z.abs().max(1).values.numpy())
                 if abort_early and i % every == 0:
                     L = float((loss1 + l2).sum())
+                    tr["check_margin"][outer][ci].append(abs(L - 0.9999 * prev) / prev)
                     if L > prev * 0.9999:
-                        abort_iters[outer][ci] = i
+                        abort_iters[outer][ci] = stopped = i
                         break
                     prev = L
+                tr["success_margin"][sl, outer, i] = success_margin(Z, t, confidence, targeted)
                 succ = _success(Z, t, confidence, targeted)
                 score = Z.argmax(1).numpy()
                 l2n = l2.numpy()
@@ -200,7 +263,12 @@ def cw_l2(layers, params, x, labels=None, targeted=False, batch_size=1, confiden
                     if l2n[e] < o_bestl2[s + e] and succ[e]:
                         o_bestl2[s + e], o_bestscore[s + e] = l2n[e], score[e]
                         x_adv[s + e] = newimg[e]
+            bestscore = step_bestscore(bestscore, stopped)
+            tr["step_success"][sl, outer] = (bestscore != -1) & ((bestscore == t) if targeted else (bestscore != t))
             const, lower, upper = const_update(bestscore, t, const, lower, upper, targeted)
         const_all[sl] = const
-    return {"x_adv": x_adv.numpy(), "best_l2": o_bestl2, "best_class": o_bestscore, "const": const_all, "abort_iters": abort_iters,
-            "labels": t_all}
+    out = {"x_adv": x_adv.numpy(), "best_l2": o_bestl2, "best_class": o_bestscore, "const": const_all, "abort_iters": abort_iters,
+           "labels": t_all}
+    if trace:
+        out["trace"] = tr
+    return out

@@ -145,3 +145,253 @@ def test_generate_on_a_defended_model_raises():
     m.rec_layer = object()                                  # what add_rec_model installs; never entered
     with pytest.raises(NotImplementedError, match="ReconstructionLayer"):
         nb.CarliniWagnerL2(m).generate(np.zeros((1, 28, 28, 1), np.float32))
+
+
+# ---------------------------------------------------------------------- the trace: margins of the decisions, by hand
+def test_margins_by_hand():
+    Z = torch.tensor([[2.0, 1.5, -1.0], [0.25, 3.0, 2.0]], dtype=torch.float64)
+    t = np.array([0, 0])
+    # untargeted, kappa 1: Z'_0 = 3 / 1.25; against the best other entry 1.5 / 3
+    np.testing.assert_allclose(R.success_margin(Z, t, 1.0, False), [1.5, 1.75], rtol=1e-15)
+    # targeted, kappa 1: Z'_0 = 1 / -0.75
+    np.testing.assert_allclose(R.success_margin(Z, t, 1.0, True), [0.5, 3.75], rtol=1e-15)
+    # arg = real - oth + kappa = 2 - 1.5 + 1, 0.25 - 3 + 1; targeted oth - real + kappa = -0.5 + 1, 2.75 + 1
+    np.testing.assert_allclose(R.arg_margin(Z, t, 1.0, False), [1.5, 1.75], rtol=1e-15)
+    np.testing.assert_allclose(R.arg_margin(Z, t, 1.0, True), [0.5, 3.75], rtol=1e-15)
+    np.testing.assert_allclose(R.arg_margin(Z, np.array([1, 2]), 0.25, False), [0.25, 0.75], rtol=1e-15)   # 1.5 - 2 + .25, 2 - 3 + .25
+
+
+def test_tie_seed_by_hand_two_and_three_maximisers():
+    """One image, n = 6, the label at 0: +c at the label, -c/2 and -c/3 at the maximisers (TF's _MaxGrad), nothing elsewhere."""
+    c = 6.0
+    two = torch.tensor([[1.0, 0.5, 0.5, -0.25, -0.25, -0.25]], dtype=torch.float64)
+    three = torch.tensor([[1.0, 0.25, 0.25, 0.75, 0.75, 0.75]], dtype=torch.float64)
+    t = np.array([0])
+    loss1, seed = R.loss1_and_seed(two, t, [c], 0.0, False)
+    assert seed.tolist() == [[c, -c / 2, -c / 2, 0, 0, 0]] and float(loss1[0]) == c * 0.5
+    loss1, seed = R.loss1_and_seed(three, t, [c], 0.0, False)
+    assert seed.tolist() == [[c, 0, 0, -c / 3, -c / 3, -c / 3]] and float(loss1[0]) == c * 0.25
+    _, seed = R.loss1_and_seed(three, t, [c], 0.0, True)                   # targeted: oth - real < 0, no gradient at all
+    assert not seed.any()
+    _, seed = R.loss1_and_seed(three, t, [c], 0.5, True)                   # kappa lifts the argument above 0: the signs turn
+    assert seed.tolist() == [[-c, 0, 0, c / 3, c / 3, c / 3]]
+    # the label inside a tied pair: its own entry is masked out of the max, the other member takes the whole share
+    _, seed = R.loss1_and_seed(two, np.array([1]), [c], 0.75, False)       # real .5, oth 1 (entry 0): arg = .25
+    assert seed.tolist() == [[-c, c, 0, 0, 0, 0]]
+    _, seed = R.loss1_and_seed(torch.tensor([[0.0, 0.5, 0.5, 0.1, 0.1, 0.1]], dtype=torch.float64), np.array([1]), [c], 0.75, False)
+    assert seed.tolist() == [[0, c, -c, 0, 0, 0]]
+
+
+def test_trace_of_a_hand_made_run():
+    """Linear(2) on one pixel, logits (2 p, 1): the label 0 is on top while p > 0.5.  Two outer steps of three iterations with a
+    check at each: shapes, NaN where no decision was taken, the check margin of the first check against prev = 1e6."""
+    layers = [("flatten",), ("linear", 2)]
+    params = [(np.array([[2.0, 0.0]]), np.array([0.0, 1.0]))]
+    x = np.full((1, 1, 1, 1), 0.75)
+    out = R.cw_l2(layers, params, x, labels=np.array([0]), batch_size=1, binary_search_steps=2, max_iterations=3, abort_early=True,
+                  initial_const=1.0, learning_rate=0.05, trace=True)
+    tr = out["trace"]
+    assert tr["success_margin"].shape == tr["arg_margin"].shape == (1, 2, 3) and tr["step_success"].shape == (1, 2)
+    p0 = (np.tanh(np.arctanh((0.75 * 2 - 1) * 0.999999)) + 1) / 2
+    np.testing.assert_allclose(tr["arg_margin"][0, :, 0], 2 * p0 - 1, rtol=1e-12)          # real - oth = 2 p - 1 at w = 0
+    np.testing.assert_allclose(tr["success_margin"][0, 0, 0], 2 * p0 - 1, rtol=1e-12)
+    L0 = 1.0 * (2 * p0 - 1)                                                                # loss1 + l2, l2 = 0 at w = 0
+    np.testing.assert_allclose(tr["check_margin"][0][0][0], abs(L0 - 0.9999 * 1e6) / 1e6, rtol=1e-12)
+    assert len(tr["check_margin"][0][0]) == 3 and out["abort_iters"] == [[None], [None]]
+    assert not tr["step_success"].any() and tr["max_logit"][0] >= 2 * p0
+    without = R.cw_l2(layers, params, x, labels=np.array([0]), batch_size=1, binary_search_steps=2, max_iterations=3, abort_early=True,
+                      initial_const=1.0, learning_rate=0.05)
+    assert sorted(without) == ["abort_iters", "best_class", "best_l2", "const", "labels", "x_adv"]     # what it returned before
+    # a stop: lr so large that the loss rises; the stopping iteration takes no success decision (NaN), later ones nothing at all
+    out = R.cw_l2(layers, params, x, labels=np.array([0]), batch_size=1, binary_search_steps=1, max_iterations=4, abort_early=True,
+                  initial_const=0.01, learning_rate=3.0, trace=True)
+    stop = out["abort_iters"][0][0]
+    assert stop is not None and 0 < stop < 3
+    tr = out["trace"]
+    assert np.isfinite(tr["success_margin"][0, 0, :stop]).all() and np.isnan(tr["success_margin"][0, 0, stop:]).all()
+    assert np.isfinite(tr["arg_margin"][0, 0, :stop + 1]).all() and np.isnan(tr["arg_margin"][0, 0, stop + 1:]).all()
+    assert len(tr["check_margin"][0][0]) == stop + 1
+
+
+# ---------------------------------------------------------------------- the cases of the GPU edge tests, on the reference alone
+from tests.support import cw_cases as K      # noqa: E402
+
+
+class _patched(object):
+    """R.<name> replaced for the length of a with block, as the spy above does."""
+
+    def __init__(self, **repl):
+        self.repl = repl
+
+    def __enter__(self):
+        self.orig = {k: getattr(R, k) for k in self.repl}
+        for k, v in self.repl.items():
+            setattr(R, k, v)
+
+    def __exit__(self, *exc):
+        for k, v in self.orig.items():
+            setattr(R, k, v)
+
+
+_loss1_and_seed, _success_rule, _tanh_space = R.loss1_and_seed, R._success, R.to_tanh_space
+
+
+def _seed_mutant(split=True, mask_label=True):
+    """loss1_and_seed with the max's share not split over its maximisers, or with the label's own entry counted among them (it
+    takes a share, which the others lose)."""
+    def mutant(Z, t, const, confidence, targeted):
+        loss1, _ = _loss1_and_seed(Z, t, const, confidence, targeted)
+        B, n = Z.shape
+        onehot = torch.zeros(B, n, dtype=Z.dtype)
+        onehot[torch.arange(B), torch.as_tensor(t)] = 1
+        real = (onehot * Z).sum(1)
+        o = (1 - onehot) * Z - onehot * 10000
+        oth = o.max(1).values
+        arg = (oth - real + confidence) if targeted else (real - oth + confidence)
+        c = torch.as_tensor(np.asarray(const, np.float64))
+        sel = ((o if mask_label else Z) == oth[:, None]).to(Z.dtype)
+        share = (sel / sel.sum(1, keepdim=True) if split else sel) * (1 - onehot)
+        sgn = -1.0 if targeted else 1.0
+        return loss1, ((arg > 0).to(Z.dtype) * c)[:, None] * (sgn * onehot - sgn * share)
+    return mutant
+
+
+MUTANTS = {
+    "kappa ignored in the success rule": dict(_success=lambda Z, t, confidence, targeted: _success_rule(Z, t, 0.0, targeted)),
+    "kappa ignored in arg": dict(loss1_and_seed=lambda Z, t, const, confidence, targeted: _loss1_and_seed(Z, t, const, 0.0, targeted)),
+    "the share not split": dict(loss1_and_seed=_seed_mutant(split=False)),
+    "the label's entry taking a share": dict(loss1_and_seed=_seed_mutant(mask_label=False)),
+    "prev / abort_iter not reset": dict(rearm=lambda prev, stopped: (prev, stopped)),
+    "bestscore of a stopped step dropped": dict(step_bestscore=lambda bs, stopped: bs if stopped is None else np.full_like(bs, -1)),
+    "the own label a later member of the tie": dict(own_label=lambda Z: Z.shape[1] - 1 - np.argmax(Z[:, ::-1], axis=1)),
+    "x not clipped before atanh": dict(to_tanh_space=lambda xc, lo, hi: torch.atanh((((xc - lo) / (hi - lo)) * 2 - 1) * 0.999999)),
+}
+# which bug each case is meant to catch (b-i1..3 and f-good carry none: on the reference alone they are shown sensitive to nothing
+# but the recorded class): five iterations at kappa = 5 never succeed under either rule for arg, so those two cases
+# stand for the success rule alone; the first iterates of the tie case (b-i1..3) hold too few successes to show a wrong share
+CASE_MUTANTS = ([(n, "kappa ignored in the success rule") for n in K.A_NAMES]
+                + [(n, "kappa ignored in arg") for n in K.A_NAMES if not n.endswith("k5.0-i5")]
+                + [("b-i6", "the share not split"), ("b-own", "the share not split"), ("b-own", "the label's entry taking a share")]
+                + [(K.OWN_K0, "the own label a later member of the tie")]
+                + [(n, "x not clipped before atanh") for n in K.C_NAMES]
+                + [(n, m) for n in K.D_NAMES for m in ("prev / abort_iter not reset", "bestscore of a stopped step dropped")])
+
+
+@pytest.mark.parametrize("name", K.NAMES)
+def test_edge_case_is_decidable(name):
+    """No chunk and at most one image in eight comes within 1e-4 of its largest |logit| (1e-5 for an abort check) of deciding the
+    other way; with fewer than eight images, none."""
+    ref = K.reference(name)
+    keep, chunks_ok = K.decidable(ref)
+    assert chunks_ok, ref["trace"]["check_margin"]
+    assert (~keep).sum() <= len(keep) // 8, np.flatnonzero(~keep)
+
+
+@pytest.mark.parametrize("name,mutant", CASE_MUTANTS)
+def test_edge_case_would_catch(name, mutant):
+    """The reference with one rule broken misses the GPU test's gates, by more than ten times, on a quarter of the images."""
+    ref = K.reference(name)
+    with _patched(**MUTANTS[mutant]):
+        bad = K.run(name)
+    d = K.differs(ref, bad, K.case(name)["kw"]["batch_size"])
+    assert d.sum() * 4 >= len(d), (int(d.sum()), len(d))
+
+
+@pytest.mark.parametrize("name", K.A_NAMES)
+def test_confidence_cases_exercise_the_success_rule(name):
+    """On at least three images some iteration succeeds at kappa = 0 but not at the tested kappa, on the SAME logits (the run at
+    the tested kappa, judged by both rules)."""
+    seen = []
+
+    def spy(Z, t, confidence, targeted):
+        with_k = _success_rule(Z, t, confidence, targeted)
+        seen.append(_success_rule(Z, t, 0.0, targeted) & ~with_k)
+        return with_k
+    with _patched(_success=spy):
+        K.run(name)
+    assert np.any(seen, axis=0).sum() >= 3
+
+
+def test_tie_cases_hold_what_they_are_for():
+    for m in "TU":
+        Z = K.reference_logits(m, K.images(m, 16, 61))
+        assert (Z[:, 1] == Z[:, 2]).all() and (Z[:, 3] == Z[:, 4]).all() and (Z[:, 3] == Z[:, 5]).all()
+    # labels 0: successes whose recorded class is a tied maximum, of both groups, first seen at different iterations
+    first = {}
+    for name in K.B_NAMES:
+        ref = K.reference(name)
+        for e in np.flatnonzero(ref["best_class"] != -1):
+            first.setdefault(int(e), int(name[3:]))
+        assert set(ref["best_class"]) <= {-1, 1, 3}                        # the lowest index of either tied group
+    assert len(set(first.values())) >= 3 and {1, 3} <= set(K.reference("b-i6")["best_class"])
+    # the model's own labels: at least four images whose top two logits tie, labelled with the first of them
+    own = K.reference("b-own")
+    assert set(own["labels"]) <= {0, 1, 3} and (own["labels"] != 0).sum() >= 4
+    assert {1, 3} <= set(own["labels"])
+    # the same at kappa = 0, where the choice among the tied members decides the outcome: labelled with the first, a tied image
+    # has arg = 0 and a first argmax equal to its label for ever (margins exactly 0, exact on both sides); labelled with a later
+    # member it succeeds on the spot at l2 = 0.  The other images are decidable in the usual sense.
+    k0 = K.reference(K.OWN_K0)
+    tied = K.tied_own(k0)
+    keep, chunks_ok = K.decidable(k0)
+    assert chunks_ok and tied.sum() >= 4 and (~keep[~tied]).sum() <= (~tied).sum() // 8
+    assert (k0["trace"]["arg_margin"][tied] == 0).all() and (k0["trace"]["success_margin"][tied] == 0).all()
+    assert (k0["best_class"][tied] == -1).all() and (k0["best_l2"][tied] == 1e10).all()
+    assert np.array_equal(k0["x_adv"][tied], K.case(K.OWN_K0)["x"].astype(np.float64)[tied])
+    with _patched(**MUTANTS["the own label a later member of the tie"]):
+        late = K.run(K.OWN_K0)
+    assert set(late["labels"][tied]) == {2, 5} and (late["best_l2"][tied] == 0).all() and (late["best_class"][tied] != -1).all()
+
+
+def test_clip_cases_hold_what_they_are_for():
+    for name in K.C_NAMES:
+        c = K.case(name)
+        lo, hi = c["kw"]["clip_min"], c["kw"]["clip_max"]
+        x = c["x"].reshape(16, -1)
+        P = x.shape[1]
+        assert ((x < lo).sum(1) >= P // 5).all() and ((x > hi).sum(1) >= P // 5).all()
+        assert ((x == lo).sum(1) >= P // 10).all() and ((x == hi).sum(1) >= P // 10).all()
+        ref = K.reference(name)
+        assert 0 < (ref["best_class"] != -1).sum() < 16                    # successes to compare, failures that return clip(x)
+        assert ref["x_adv"].min() >= lo and ref["x_adv"].max() <= hi
+
+
+def test_degenerate_schedules_of_the_reference():
+    for name in ("c-T-11", "c-F-01"):
+        c = K.case(name)
+        lo, hi = c["kw"]["clip_min"], c["kw"]["clip_max"]
+        zero_it = K.run(name, max_iterations=0, binary_search_steps=2)
+        zero_steps = K.run(name, binary_search_steps=0)
+        for out in (zero_it, zero_steps):
+            assert np.array_equal(out["x_adv"], np.clip(c["x"].astype(np.float64), lo, hi))
+            assert (out["best_l2"] == 1e10).all() and (out["best_class"] == -1).all()
+        assert (zero_steps["const"] == c["kw"]["initial_const"]).all() and zero_steps["abort_iters"] == []
+        assert (zero_it["const"] == c["kw"]["initial_const"] * 100).all()   # the failure branch, twice
+        assert zero_it["abort_iters"] == [[None], [None]]
+
+
+@pytest.mark.parametrize("name", K.D_NAMES)
+def test_abort_cases_stop_at_different_checks_and_also_run_to_the_end(name):
+    stop = np.array(K.stops(K.reference(name)))                             # [outer step, chunk]
+    assert stop.shape == (3, 3)
+    assert any(len(set(col[col >= 0])) >= 2 for col in stop.T), stop        # a chunk that stops at different checks
+    assert (stop == -1).any() and (stop >= 0).any(), stop                   # one that runs to the end in some step
+    every = max(K.case(name)["kw"]["max_iterations"] // 10, 1)
+    assert (stop[stop >= 0] % every == 0).all()
+
+
+def test_bad_label_case_of_the_reference():
+    c = K.bad_label_case()
+    assert [c["labels"][i] for i in c["bad"]] == [-1, 10, 0x7fffffff] and c["labels"].dtype == np.int32
+    n = len(K.reference_logits("F", c["x"])[0])
+    assert all(not 0 <= c["labels"][i] < n for i in c["bad"]) and all(0 <= c["labels"][i] < n for i in c["good"])
+    # the good rows carry their own classes, so nothing succeeds at iteration 0 and the later iterations show in the outputs:
+    # one row succeeds after some Adam steps (l2 > 0), the other never, and the search moves their constants apart
+    assert K.own_labels("F", c["x"])[c["good"]].tolist() == [3, 1]
+    ref = K.reference("f-good")
+    assert ref["best_class"].tolist().count(-1) == 1 and (ref["best_l2"] > 0).all() and ref["const"][0] != ref["const"][1]
+    # what the device must return for the bad rows' constant: the failure branch, once per outer step
+    const, lower, upper = np.full(3, c["kw"]["initial_const"]), np.zeros(3), np.full(3, 1e10)
+    for _ in range(c["kw"]["binary_search_steps"]):
+        const, lower, upper = R.const_update(np.full(3, -1), c["labels"][c["bad"]], const, lower, upper, False)
+    assert (const == c["kw"]["initial_const"] * 100).all()
