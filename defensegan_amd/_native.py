@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libdefensegan_hip.so")
 MEASURE_LIB_PATH = os.path.join(_HERE, "lib", "libdefensegan_hip_measure.so")
 
 DG_OK = 0
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 # every symbol include/defensegan_hip.h declares: (name, restype, argtypes)
 _vp, _i, _i64, _u64, _f, _cp = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_char_p
@@ -58,6 +58,7 @@ SYMBOLS = [
     ("dg_clf_get_weights", _i, [_vp, _i, _vp, _vp, _i]),
     ("dg_clf_adam_reset", _i, [_vp]),
     ("dg_clf_get_adam", _i, [_vp, _i, _vp, _vp, C.POINTER(_i64), _i]),
+    ("dg_clf_set_adam", _i, [_vp, _i, _vp, _vp, _i64, _i]),
     ("dg_clf_dropout_mask", _i, [_vp, _i, _i, _u64, _i64, _i, _vp, _vp]),
     ("dg_clf_param_gradient", _i, [_vp, _vp, _vp, _i, _f, _f, _f, _u64, _i64, _vp, _vp, _vp, _vp]),
     ("dg_clf_train", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _f, _u64, _vp, _vp]),
@@ -71,6 +72,8 @@ SYMBOLS = [
     ("dg_bpda_step_ball", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _f, _f, _vp, _vp]),
     ("dg_pgd_ball", _i, [_vp, _vp, _vp, _vp, _i, _f, _f, _i, _i, _f, _f, _vp, _vp, _vp]),
     ("dg_row_norms", _i, [_vp, _vp, _i, _i64, _i, _vp, _vp]),
+    ("dg_critic_gradient", _i, [_vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    ("dg_critic_step", _i, [_vp, _vp, _vp, _vp, _i, _f, _i, _f, _f, _f, _vp, _vp]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

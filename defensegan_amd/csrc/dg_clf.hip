@@ -78,6 +78,14 @@ __global__ __launch_bounds__(256) void clf_relu_kernel(const float* __restrict__
     if (i < total) y[i] = x[i] > 0.f ? x[i] : 0.f;
 }
 
+// The critic's LeakyReLU, tf.maximum(0.2 x, x) (models/dataset_models.py:10-11; 0.2 is the reference's only slope)
+__global__ __launch_bounds__(256) void clf_leaky_relu_kernel(const float* __restrict__ x, float* __restrict__ y, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const float v = x[i], a = 0.2f * v;
+    y[i] = a > v ? a : v;              // a NaN stays a NaN, as in tf.maximum
+}
+
 // tf.nn.softmax over the last axis; one thread per row (the class count is small)
 __global__ __launch_bounds__(64) void clf_softmax_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int n) {
     const int b = blockIdx.x * 64 + threadIdx.x;
@@ -202,6 +210,14 @@ __global__ __launch_bounds__(256) void clf_relu_bwd_kernel(const float* __restri
     if (i < total) dx[i] = out[i] > 0.f ? g[i] : 0.f;
 }
 
+// LeakyReLU's gradient from its own output: out has the sign of the input, so out > 0 passes g and everything else gets the
+// slope 0.2 -- an input of exactly 0 included: TF's MaximumGrad gives a tie to the first argument, 0.2 x
+__global__ __launch_bounds__(256) void clf_leaky_relu_bwd_kernel(const float* __restrict__ g, const float* __restrict__ out,
+                                                                  float* __restrict__ dx, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) dx[i] = out[i] > 0.f ? g[i] : 0.2f * g[i];
+}
+
 // x_adv = clip(x + eps * sign(grad), lo, hi)   (cleverhans fgm with ord = inf; sign(0) = 0 as tf.sign)
 __global__ __launch_bounds__(256) void clf_fgsm_kernel(const float* __restrict__ x, const float* __restrict__ grad,
                                                         float* __restrict__ xadv, long long total, float eps, float lo, float hi) {
@@ -232,8 +248,21 @@ void clf_launch_forward(const dg_clf* h, int j, const float* in, float* out, int
                            l.oc, l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
     else if (l.kind == DG_LAYER_LINEAR)
         hipLaunchKernelGGL(clf_linear_kernel, dim3(grid), dim3(256), 0, s, in, l.W, l.b, out, total, l.cin, l.cout, l.fused_relu ? 1 : 0);
+    else if (l.kind == DG_LAYER_LEAKY_RELU)
+        hipLaunchKernelGGL(clf_leaky_relu_kernel, dim3(grid), dim3(256), 0, s, in, out, total);
     else
         hipLaunchKernelGGL(clf_relu_kernel, dim3(grid), dim3(256), 0, s, in, out, total);
+}
+
+void clf_launch_linear_part(const dg_clf* h, int j, const float* in, const float* zero_bias, float* out, int B, hipStream_t s) {
+    const ClfLayer& l = h->layers[j];
+    const long long total = (long long)B * l.features();
+    const unsigned grid = (unsigned)((total + 255) / 256);
+    if (l.kind == DG_LAYER_CONV2D)
+        hipLaunchKernelGGL(clf_conv2d_kernel, dim3(grid), dim3(256), 0, s, in, l.W, zero_bias, out, total, l.ih, l.iw, l.ic, l.oh, l.ow,
+                           l.oc, l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, 0);
+    else
+        hipLaunchKernelGGL(clf_linear_kernel, dim3(grid), dim3(256), 0, s, in, l.W, zero_bias, out, total, l.cin, l.cout, 0);
 }
 
 void clf_launch_input_grad(const dg_clf* h, int j, const float* g, const float* out, float* dx, int B, hipStream_t s) {
@@ -245,6 +274,8 @@ void clf_launch_input_grad(const dg_clf* h, int j, const float* g, const float* 
     else if (l.kind == DG_LAYER_CONV2D)
         hipLaunchKernelGGL(clf_conv2d_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, l.W, dx, total, l.ih, l.iw, l.ic, l.oh, l.ow, l.oc,
                            l.kh, l.kw, l.sh, l.sw, l.pad_t, l.pad_l, l.fused_relu ? 1 : 0);
+    else if (l.kind == DG_LAYER_LEAKY_RELU)
+        hipLaunchKernelGGL(clf_leaky_relu_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, dx, total);
     else
         hipLaunchKernelGGL(clf_relu_bwd_kernel, dim3(grid), dim3(256), 0, s, g, out, dx, total);
 }
@@ -368,6 +399,7 @@ int dg_clf_destroy(dg_clf* h) {
     jac_release(h->jac);
     bpda_release(h->bpda);
     pgd_release(h->pgd);
+    critic_release(h->critic);
     delete h;
     return DG_OK;
 }
@@ -412,7 +444,7 @@ int dg_clf_add_layer(dg_clf* h, int kind, int p0, int p1, int p2, int p3, int p4
             l.oh = l.ow = 1; l.oc = l.ih * l.iw * l.ic; l.skip = true;       // NHWC row-major: a reshape, no data movement
             h->flat = true;
             break;
-        case DG_LAYER_RELU: case DG_LAYER_SOFTMAX: case DG_LAYER_DROPOUT:
+        case DG_LAYER_RELU: case DG_LAYER_SOFTMAX: case DG_LAYER_DROPOUT: case DG_LAYER_LEAKY_RELU:      // LeakyReLU: a kernel of its own
             l.oh = l.ih; l.ow = l.iw; l.oc = l.ic;
             if (kind == DG_LAYER_DROPOUT) l.skip = true;                             // K.learning_phase() == 0 at evaluation
             if (kind == DG_LAYER_RELU && !h->layers.empty()) {

@@ -1,6 +1,6 @@
-// The classifier handle as its seven source files see it: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
+// The classifier handle as its eight source files see it: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
 // dg_cw.hip (the Carlini-Wagner attack), dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation), dg_bpda.hip (the BPDA/EOT step), dg_pgd.hip (PGD on the bare
-// classifier) and dg_ball.hip (the per-image norms and steps of the L1 / L2 attacks).  Everything here is internal to the library: plain C++
+// classifier), dg_ball.hip (the per-image norms and steps of the L1 / L2 attacks) and dg_critic.hip (the WGAN-GP critic's cost, gradient and step).  Everything here is internal to the library: plain C++
 // under hidden visibility, nothing of it is exported.
 #pragma once
 
@@ -38,6 +38,7 @@ struct TrainWork;    // dg_clf_train.hip
 struct JacWork;      // dg_jacobian.hip
 struct BpdaWork;     // dg_bpda.hip
 struct PgdWork;      // dg_pgd.hip
+struct CriticWork;   // dg_critic.hip
 
 struct dg_clf {
     int device = 0;
@@ -63,6 +64,7 @@ struct dg_clf {
     JacWork* jac = nullptr;                   // class-gradient seed, grown on demand
     BpdaWork* bpda = nullptr;                 // BPDA's cross-entropy seed, grown on demand
     PgdWork* pgd = nullptr;                   // PGD's seed and its two iterate buffers, grown on demand
+    CriticWork* critic = nullptr;             // the WGAN-GP critic's three-batch workspace, grown on demand
 
     int pixels() const { return in_h * in_w * in_c; }
 };
@@ -95,6 +97,8 @@ int clf_grow(T** p, int n, size_t& cap, size_t need) {
 int clf_missing_weights(const dg_clf* h);          // the first Conv2D / Linear layer without weights, or -1
 // layer j's evaluation kernel (Conv2D / Linear with its fused ReLU, or an unfused ReLU): in [B, ih, iw, ic] -> out [B, oh, ow, oc]
 void clf_launch_forward(const dg_clf* h, int j, const float* in, float* out, int B, hipStream_t s);
+// layer j's Conv2D / Linear map alone: its bias replaced by zero_bias [cout] and no fused ReLU (the critic's tangent pass)
+void clf_launch_linear_part(const dg_clf* h, int j, const float* in, const float* zero_bias, float* out, int B, hipStream_t s);
 // layer j's input gradient: dx = d/din of sum(g * out), out = the layer's kept output
 void clf_launch_input_grad(const dg_clf* h, int j, const float* g, const float* out, float* dx, int B, hipStream_t s);
 // dCE/dlogits with the label or (labels == NULL) the model's own first argmax
@@ -111,6 +115,23 @@ void train_release(TrainWork* w);    // dg_clf_train.hip
 void jac_release(JacWork* w);        // dg_jacobian.hip
 void bpda_release(BpdaWork* w);      // dg_bpda.hip
 void pgd_release(PgdWork* w);        // dg_pgd.hip
+void critic_release(CriticWork* w);  // dg_critic.hip
+
+// ---- dg_clf_train.hip -------------------------------------------------------------------------------------------------------------
+// How a Conv2D / Linear layer's weight gradient over B images is cut: `slots` runs of kc terms of its reduction axis, each slot
+// leaving `per` = (M + 1) * N partial sums of (dW; db).  The same B always gives the same plan.
+struct ClfWgradPlan {
+    int slots = 0, kc = 0;
+    size_t per = 0;
+};
+ClfWgradPlan train_wgrad_plan(const ClfLayer& v, int B);
+// part [slots, per] = the partial sums of layer v's (dW; db) for its inputs x [B, ...] and output gradients g [B, features], g masked
+// by out > 0 where the layer's ReLU is fused.  bias_row false: the db row is left zero (a term that carries no bias gradient).
+void train_launch_wgrad(const ClfLayer& v, const float* x, const float* g, const float* out, int B, const ClfWgradPlan& p, float* part,
+                        bool bias_row, hipStream_t s);
+// The handle's Adam state, created (zero, t = 0) on first use: per layer index the moments [(W; b)] of a Conv2D / Linear layer,
+// and the step count.  Fetch them per call: adding a layer moves them.
+int train_adam_state(dg_clf* h, float*** m, float*** v, long long** t);
 
 // ---- shared by the attack steps (dg_bpda.hip, dg_ball.hip) -------------------------------------------------------------------------
 // the final clip of every attack step: clip(v, lo, hi) with lo <= hi

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64) void tr_loss_kernel(const float* __restrict__ c
 
 // ---- weight gradients: an implicit GEMM per Conv2D / Linear layer -------------------------------------------------------------
 // part[z, m, n] = sum_{k in slot z} A[k, m] * G[k, n], k = (b, yo, xo) of the layer output, m = (a, c, ci) of the kernel (row M: the
-// bias, A = 1), n = co; A[k, (a,c,ci)] = x[b, yo*sh + a - pt, xo*sw + c - pl, ci] (0 in the padding), G = gm.  A Linear layer is a
+// bias, A = bias_one), n = co; A[k, (a,c,ci)] = x[b, yo*sh + a - pt, xo*sw + c - pl, ci] (0 in the padding), G = gm.  A Linear layer is a
 // 1x1 convolution of a 1x1 image.  64 x 64 output tiles, 256 threads with a 4 x 4 register tile each, k in chunks of 16 through LDS;
 // slot z owns k in [z Kc, (z + 1) Kc) and sums it in order.  The k index of a thread's loads depends on its wave only, so the
 // (b, yo, xo) decode is wave-uniform.
@@ -136,7 +136,8 @@ struct WGeo {
 constexpr int WT = 64, WKC = 16;
 
 __global__ __launch_bounds__(256) void tr_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                        const float* __restrict__ out, int relu, float* __restrict__ part, WGeo q) {
+                                                        const float* __restrict__ out, int relu, float bias_one,
+                                                        float* __restrict__ part, WGeo q) {
     __shared__ __attribute__((aligned(16))) float As[WKC][WT];
     __shared__ __attribute__((aligned(16))) float Gs[WKC][WT];
     const int tid = threadIdx.x;
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(256) void tr_wgrad_kernel(const float* __restrict__
             float av = 0.f, gv = 0.f;
             if (k < kend) {
                 if (is_b) {
-                    av = 1.f;
+                    av = bias_one;                 // 1, or 0 for a term without a bias gradient (the critic's penalty)
                 } else if (is_w) {
                     const int xo = k % q.ow, t1 = k / q.ow;
                     const int yo = t1 % q.oh, b = t1 / q.oh;
@@ -235,7 +236,7 @@ struct Plan {
 };
 
 // a layer that writes an output in the training phase (Dropout does, other than at evaluation)
-bool has_output(const ClfLayer& v) { return v.has_params() || v.kind == DG_LAYER_DROPOUT || (v.kind == DG_LAYER_RELU && !v.skip); }
+bool has_output(const ClfLayer& v) { return v.has_params() || v.kind == DG_LAYER_DROPOUT || ((v.kind == DG_LAYER_RELU || v.kind == DG_LAYER_LEAKY_RELU) && !v.skip); }
 
 WGeo geometry(const ClfLayer& v, int B) {
     WGeo q;
@@ -370,12 +371,11 @@ const float* backward_pass(dg_clf* h, TrainWork* w, const Plan& p, const float* 
         const ClfLayer& v = h->layers[j];
         if (!has_output(v)) continue;
         if (half >= 0 && v.has_params()) {
-            WGeo q = geometry(v, B);
-            q.Kc = w->kc[j];
-            const int S = w->slots[j];
-            float* part = w->part[j] + (size_t)half * S * (q.M + 1) * q.N;
-            hipLaunchKernelGGL(tr_wgrad_kernel, dim3((unsigned)((q.M + 1 + WT - 1) / WT), (unsigned)((q.N + WT - 1) / WT), (unsigned)S),
-                               dim3(256), 0, s, w->in[j], g, w->act[j], v.fused_relu ? 1 : 0, part, q);
+            ClfWgradPlan wp;
+            wp.slots = w->slots[j];
+            wp.kc = w->kc[j];
+            wp.per = param_floats(v);
+            train_launch_wgrad(v, w->in[j], g, w->act[j], B, wp, w->part[j] + (size_t)half * wp.slots * wp.per, true, s);
         }
         if (!to_input && j <= p.first_param) break;              // nothing below needs a gradient
         float* dx = w->gbuf[which ^ 1];
@@ -444,6 +444,31 @@ int prepare(dg_clf* h, Plan* p, int B) {
 
 }  // namespace
 
+ClfWgradPlan train_wgrad_plan(const ClfLayer& v, int B) {
+    ClfWgradPlan p;
+    slot_plan(geometry(v, B), &p.slots, &p.kc);
+    p.per = param_floats(v);
+    return p;
+}
+
+void train_launch_wgrad(const ClfLayer& v, const float* x, const float* g, const float* out, int B, const ClfWgradPlan& p, float* part,
+                        bool bias_row, hipStream_t s) {
+    WGeo q = geometry(v, B);
+    q.Kc = p.kc;
+    hipLaunchKernelGGL(tr_wgrad_kernel, dim3((unsigned)((q.M + 1 + WT - 1) / WT), (unsigned)((q.N + WT - 1) / WT), (unsigned)p.slots),
+                       dim3(256), 0, s, x, g, out, v.fused_relu ? 1 : 0, bias_row ? 1.f : 0.f, part, q);
+}
+
+int train_adam_state(dg_clf* h, float*** m, float*** v, long long** t) {
+    Plan p;
+    int rc = prepare(h, &p, 1);
+    if (rc) return rc;
+    *m = h->tr->m.data();
+    *v = h->tr->v.data();
+    *t = &h->tr->t;
+    return DG_OK;
+}
+
 void train_release(TrainWork* w) {
     if (!w) return;
     auto drop = [](auto& vec) {
@@ -487,6 +512,22 @@ int dg_clf_get_adam(dg_clf* h, int layer, float* m, float* v, int64_t* t, int is
     if (m) CLF_TRY(hipMemcpy(m, w->m[layer], per * sizeof(float), kind));
     if (v) CLF_TRY(hipMemcpy(v, w->v[layer], per * sizeof(float), kind));
     if (t) *t = w->t;
+    return DG_OK;
+}
+
+int dg_clf_set_adam(dg_clf* h, int layer, const float* m, const float* v, int64_t t, int is_device) {
+    if (!h || !m || !v || t < 0) return clf_fail(DG_E_INVALID, "dg_clf_set_adam: bad argument");
+    Plan p;
+    int rc = prepare(h, &p, 1);
+    if (rc) return rc;
+    TrainWork* w = h->tr;
+    if (layer < 0 || layer >= (int)h->layers.size() || !h->layers[layer].has_params())
+        return clf_fail(DG_E_INVALID, "layer %d has no parameters", layer);
+    const size_t per = param_floats(h->layers[layer]);
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    CLF_TRY(hipMemcpy(w->m[layer], m, per * sizeof(float), kind));
+    CLF_TRY(hipMemcpy(w->v[layer], v, per * sizeof(float), kind));
+    w->t = t;
     return DG_OK;
 }
 

@@ -35,7 +35,8 @@ class DefenseGANBase(object):
     arch_name = None          # set by subclasses
 
     _default_attributes = ['dataset_name', 'batch_size', 'use_bn', 'test_batch_size', 'latent_dim',
-                           'net_dim', 'rec_iters', 'image_dim', 'rec_rr', 'rec_lr', 'debug']
+                           'net_dim', 'rec_iters', 'image_dim', 'rec_rr', 'rec_lr', 'debug',
+                           'mode', 'gradient_penalty_lambda', 'critic_iters', 'train_iters']
 
     def __init__(self, cfg=None, test_mode=False, verbose=False, device=None, measure=False, **args):
         # defaults of DefenseGANBase.__init__ (gan.py:50-68)
@@ -51,6 +52,14 @@ class DefenseGANBase(object):
         self.rec_rr = 10
         self.rec_lr = 10.0
         self.rec_momentum = 0.7            # hard-coded in the reference (gan.py:390)
+        # training (gan.py:54-57).  MODE is 'wgan-gp' in every shipped configuration of the reference (experiments/cfgs/gans/);
+        # the class default there, 'gp-wgan', matches no branch of _loss
+        self.mode = 'wgan-gp'
+        self.gradient_penalty_lambda = 10.0
+        self.critic_iters = 5
+        self.train_iters = 30000
+        self.penalty_axes = args.get("penalty_axes", "reference")      # critic.PENALTY_AXES: the reference's height-only sum
+        self._critic = None
         # "constant": lr == rec_lr throughout = what the reference executes (its decay never fires, gan.py:362-386);
         # "intended": the x0.1 staircase at ceil(0.8 * rec_iters) its code asks for.  Off by default.
         self.rec_lr_schedule = args.get("rec_lr_schedule", "constant")
@@ -130,6 +139,9 @@ class DefenseGANBase(object):
         if self._handle is not None:
             self._lib().dg_destroy(self._handle)
             self._handle = None
+        if getattr(self, "_critic", None) is not None:
+            self._critic.close()
+            self._critic = None
 
     def __del__(self):
         try:
@@ -487,6 +499,151 @@ class DefenseGANBase(object):
                                               float(std) if std else 0.0,
                                               torch.cuda.current_stream(dev).cuda_stream))
         return z
+
+    # ------------------------------------------------------------------ the critic (gan.py:121-126, 167-199, 253-329)
+    @property
+    def critic(self):
+        """The critic D (critic.mnist_discriminator at this model's net_dim and image_dim), built on first use; its weights come
+        from load_discriminator, critic.init_like_tflib or critic.set_named_weights."""
+        if self._critic is None:
+            from . import critic as _critic
+            if self._arch.arch_id == archs.ARCH_CELEBA:
+                _critic.celeba_discriminator()
+            self._critic = _critic.mnist_discriminator(net_dim=int(self.net_dim), input_shape=(None,) + tuple(self.image_dim),
+                                                       use_bn=bool(self.use_bn))
+            if self._device is not None:
+                self._critic._device = int(self._device)
+        return self._critic
+
+    def _check_mode(self):
+        if self.mode != 'wgan-gp':
+            raise NotImplementedError("MODE %r is not implemented: only 'wgan-gp' (gan.py:167-199) is" % (self.mode,))
+
+    def discriminator_fn(self, x):
+        """D(x) [B]: the critic's one output per image (gan.py:121-126)."""
+        self._ensure_handle()
+        self.critic._device = self._device
+        return self.critic.discriminate(x)
+
+    def _critic_inputs(self, B, k, seed, gen):
+        """Step k's fake batch and alpha: fake = G(z), z = the rows [k B, (k + 1) B) of the N(0, 1) draw keyed by ``seed``
+        (init_latents with std 1: the training prior tf.random_normal of models/dataset_models.py:39-40, not the projection's
+        sqrt(1 / latent));
+        alpha = the next B uniforms of the device generator ``gen``."""
+        torch = _torch()
+        z = self.init_latents(B, seed=seed, first_row=k * B, std=1.0)
+        return self.generate(z), torch.rand(B, generator=gen, device=z.device, dtype=torch.float32)
+
+    def _alpha_generator(self, seed):
+        torch = _torch()
+        gen = torch.Generator(device=torch.device("cuda", self._device))
+        gen.manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        return gen
+
+    def discriminator_cost(self, real, fake=None, alpha=None, seed=None, return_terms=False):
+        """The reference's ``discriminator_cost`` fetch (its dev cost, gan.py:300-315): mean D(fake) - mean D(real) + lambda P.
+        ``fake`` defaults to G(z), z ~ N(0, 1) [B, latent]; ``alpha`` to a seeded uniform draw made on the device.  Returns the
+        cost (with ``return_terms``: cost, w, P)."""
+        self._check_mode()
+        self._ensure_handle()
+        self.critic._device = self._device
+        x = self._to_device(real)
+        B = int(x.shape[0])
+        if seed is None:
+            seed = self._default_seed
+        if fake is None or alpha is None:
+            f, a = self._critic_inputs(B, 0, seed, self._alpha_generator(seed))
+            fake = f if fake is None else fake
+            alpha = a if alpha is None else alpha
+        cost, _, _ = self.critic.gradient(x, self._to_device(fake), self._to_device(alpha), gp_lambda=float(self.gradient_penalty_lambda),
+                                          penalty_axes=self.penalty_axes, sync=False)
+        cost = cost.cpu().numpy()
+        return tuple(float(c) for c in cost) if return_terms else float(cost[0])
+
+    def critic_schedule(self, n_images, n_steps, seed):
+        """[n_steps, batch_size] int64 image indices: a seeded permutation per epoch, cut into full batches (the tail of an epoch
+        that does not fill a batch is dropped, as the reference's generators do)."""
+        bs = int(self.batch_size)
+        per_epoch = int(n_images) // bs
+        if per_epoch < 1:
+            raise ValueError("%d images do not fill one batch of %d" % (n_images, bs))
+        rs = np.random.RandomState(int(seed) & 0xFFFFFFFF)
+        rows = []
+        while len(rows) < n_steps:
+            perm = rs.permutation(int(n_images))
+            rows.extend(perm[i * bs:(i + 1) * bs] for i in range(per_epoch))
+        return np.asarray(rows[:n_steps], np.int64).reshape(n_steps, bs)
+
+    def train(self, images, phase=None, train_iters=None, seed=None, learning_rate=1e-4, beta1=0.5, beta2=0.9):
+        """The critic half of the reference's ``train`` (gan.py:253-329), which is all it runs for a ``phase`` other than None:
+        ``train_iters`` iterations of ``critic_iters`` Adam steps (dg_critic_step; 1e-4, 0.5, 0.9) on successive batches of
+        ``batch_size`` of ``images`` [n,H,W,C] (generator range), in the order of ``critic_schedule``.  Step k takes the fake batch
+        and alpha of ``_critic_inputs(batch_size, k, seed, gen)``, gen one device generator seeded with ``seed``.  Nothing waits for
+        the device inside the loop.  Returns [train_iters, 3]: each iteration's last cost, w and P (the reference plots the first).
+        ``phase=None`` asks for generator steps as well, which are not implemented."""
+        self._check_mode()
+        if phase is None:
+            raise NotImplementedError("train(phase=None) needs the generator step (a generator backward seeded from the critic, with "
+                                      "weight gradients), which is not implemented; train(phase=...) trains the critic alone")
+        torch = _torch()
+        self._ensure_handle()
+        if not self.initialized:
+            raise _native.NativeError("generator weights not loaded (load_generator / set_weights)")
+        self.critic._device = self._device
+        iters = int(self.train_iters if train_iters is None else train_iters)
+        ci, bs = int(self.critic_iters), int(self.batch_size)
+        if seed is None:
+            seed = self._default_seed
+        x = self._to_device(images)
+        sched = torch.from_numpy(self.critic_schedule(int(x.shape[0]), iters * ci, seed)).to(x.device)
+        gen = self._alpha_generator(seed)
+        costs = torch.empty(iters, 3, dtype=torch.float32, device=x.device)
+        scratch = torch.empty(3, dtype=torch.float32, device=x.device)
+        lam = float(self.gradient_penalty_lambda)
+        for it in range(iters):
+            for i in range(ci):
+                k = it * ci + i
+                fake, alpha = self._critic_inputs(bs, k, seed, gen)
+                self.critic.step(x[sched[k]], fake, alpha, gp_lambda=lam, penalty_axes=self.penalty_axes, learning_rate=learning_rate,
+                                 beta1=beta1, beta2=beta2, cost=costs[it] if i == ci - 1 else scratch)
+        return costs.cpu().numpy()
+
+    def save_discriminator(self, path: str) -> None:
+        """An .npz of the critic: its parameters under their tflib names, Adam's moments as ``adam_m/<name>`` and ``adam_v/<name>``
+        and the step count ``adam_t``."""
+        c = self.critic
+        arrays = dict(c.named_weights())
+        t = 0
+        for (wn, bn), ((mW, mb), (vW, vb), t) in zip(c.param_names, c.adam_state()):
+            arrays["adam_m/" + wn], arrays["adam_m/" + bn] = mW, mb
+            arrays["adam_v/" + wn], arrays["adam_v/" + bn] = vW, vb
+        arrays["adam_t"] = np.asarray(t, np.int64)
+        with open(path, "wb") as fh:
+            np.savez(fh, **arrays)
+
+    def load_discriminator(self, path: str) -> None:
+        """``path``: an .npz written by save_discriminator (or holding the parameters alone: Adam then starts afresh), or a
+        reference checkpoint (directory, prefix or .index file) whose ``Discriminator.*`` variables are read by tf_checkpoint."""
+        c = self.critic
+        if self._device is not None:
+            c._device = int(self._device)
+        names = list(c.named_shapes())
+        if path.endswith(".npz"):
+            with np.load(path) as f:
+                have = {k: f[k] for k in f.files}
+        else:
+            from . import tf_checkpoint
+            have = tf_checkpoint.generator_weights(path, names)
+        c.set_named_weights(have)
+        lib = _native.load()
+        if "adam_t" not in have:
+            c.adam_reset()
+            return
+        for li, (wn, bn) in zip(c._param_layers, c.param_names):
+            m = np.ascontiguousarray(np.concatenate([have["adam_m/" + wn].reshape(-1), have["adam_m/" + bn].reshape(-1)]), np.float32)
+            v = np.ascontiguousarray(np.concatenate([have["adam_v/" + wn].reshape(-1), have["adam_v/" + bn].reshape(-1)]), np.float32)
+            _native.check(lib.dg_clf_set_adam(c._handle, c._native_index[li], m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p),
+                                              int(have["adam_t"]), 0))
 
     # ------------------------------------------------------------------ measurement hooks
     def set_option(self, key: str, value) -> None:

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _native
 
-KIND = {"Conv2D": 0, "ReLU": 1, "Linear": 2, "Flatten": 3, "Softmax": 4, "Dropout": 5}
+KIND = {"Conv2D": 0, "ReLU": 1, "Linear": 2, "Flatten": 3, "Softmax": 4, "Dropout": 5, "LeakyReLU": 6}
 
 
 class Layer(object):
@@ -56,6 +56,11 @@ class Linear(Layer):
 
 class ReLU(Layer):
     pass
+
+
+class LeakyReLU(Layer):
+    """The critic's activation, tf.maximum(0.2 * x, x) (models/dataset_models.py:10-11).  The slope 0.2 is the reference's only
+    value and is fixed in the kernel; the gradient at x == 0 is 0.2 (TF's MaximumGrad gives a tie to its first argument)."""
 
 
 class Flatten(Layer):

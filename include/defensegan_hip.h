@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DG_ABI_VERSION 1
+#define DG_ABI_VERSION 2
 
 /* architectures: /root/reference/models/dataset_models.py:36-71 (mnist, f-mnist), :127-165 (celeba) */
 #define DG_ARCH_MNIST28 0
@@ -265,6 +265,8 @@ typedef struct dg_clf dg_clf;
 #define DG_LAYER_SOFTMAX 4
 #define DG_LAYER_DROPOUT 5    /* identity: K.learning_phase() is 0 at evaluation (network_builder.py:296-297);    *
                                * active in training (dg_clf_set_dropout)                                          */
+#define DG_LAYER_LEAKY_RELU 6 /* max(0.2 x, x), the critic's activation (models/dataset_models.py:10-11); the slope is   *
+                               * fixed; its gradient is 1 for x > 0 and 0.2 for x <= 0 (TF's MaximumGrad at the tie)      */
 
 /* An empty MLP for NHWC inputs [*, in_h, in_w, in_c] (network_builder.py:129-162). */
 int dg_clf_create(int device, int in_h, int in_w, int in_c, dg_clf** out);
@@ -340,6 +342,9 @@ int dg_clf_get_weights(dg_clf* h, int layer, float* W, float* b, int is_device);
 int dg_clf_adam_reset(dg_clf* h);
 /* A layer's Adam state: m and v [(W; b) flattened, W first] and the step count t (host).  Any of m, v, t may be NULL. */
 int dg_clf_get_adam(dg_clf* h, int layer, float* m, float* v, int64_t* t, int is_device);
+/* Installs a layer's moments (the layout dg_clf_get_adam returns) and sets the handle's step count to t: what restoring a saved
+ * optimiser needs.  Synchronous. */
+int dg_clf_set_adam(dg_clf* h, int layer, const float* m, const float* v, int64_t t, int is_device);
 /* The mask [B, features] a Dropout layer draws in the forward `pass` (0 clean, 1 the adversarial half's inner FGSM forward,
  * 2 the forward on x_adv) of step `step` under `seed`: floor(keep + u), u from Philox4x32-10 (dg_clf_train.hip). */
 int dg_clf_dropout_mask(dg_clf* h, int layer, int B, uint64_t seed, int64_t step, int pass, float* mask, void* stream);
@@ -436,6 +441,30 @@ int dg_pgd_ball(dg_clf* h, const float* x, const float* x_start, const int32_t* 
 /* out [B] = per row of row_elems floats the ord-norm (1: sum |.|, 2: sqrt(sum .^2)) of v - w, or of v when w == NULL.  Runs on the
  * current device. */
 int dg_row_norms(const float* v, const float* w, int B, int64_t row_elems, int ord, float* out, void* stream);
+
+/*
+ * The WGAN-GP critic (models/gan.py:167-199, mode "wgan-gp"; defensegan_amd/csrc/dg_critic.hip's header comment and DESIGN.md
+ * section 7, "The critic", give the restatement and the derivation of the penalty's gradient).  The handle is a dg_clf model of
+ * Conv2D, LeakyReLU, ReLU, Flatten and Linear layers whose output width is 1 (defensegan_amd/critic.py builds the reference's
+ * mnist_discriminator); a model holding Dropout or Softmax, an output width other than 1, B < 1 and an unknown penalty_axes are
+ * DG_E_INVALID.  With real, fake [B,H,W,C], alpha [B] and xhat = real + alpha (fake - real):
+ *     w = mean_b D(fake_b) - mean_b D(real_b);   g = d(sum_b D(xhat_b)) / dxhat;   s = sqrt(sum over the reduced axes of g^2)
+ *     P = mean over what is left of (s - 1)^2;   cost = w + gp_lambda P
+ * penalty_axes 0 ("reference"): the sum runs over the HEIGHT axis only, as the reference's reduction_indices=[1] on an NHWC tensor
+ * has it: s is [B,W,C] and P the mean of B W C column norms.  penalty_axes 1 ("image"): the published form, s [B] over H, W, C.
+ * Where s == 0 the penalty's gradient is defined as 0 (TF yields NaN there).  Device pointers; asynchronous on `stream`, no host
+ * synchronisation, no graph capture, no float atomics: a call repeated returns the same bits.  The workspace grows on demand.
+ */
+/* grads = d cost / d(every Conv2D / Linear layer's (W; b)) in dg_clf_param_gradient's layout; cost [3] = cost, w, P; slopes
+ * (may be NULL) = s, [B,W,C] or [B].  The parameters do not change. */
+int dg_critic_gradient(dg_clf* h, const float* real, const float* fake, const float* alpha, int B, float gp_lambda,
+                       int penalty_axes, float* grads, float* cost, float* slopes, void* stream);
+/* One step of tf.train.AdamOptimizer(learning_rate, beta1 = beta_a, beta2 = beta_b, epsilon = 1e-8) on that gradient (the reference:
+ * 1e-4, 0.5, 0.9): m = beta_a m + (1 - beta_a) g, v = beta_b v + (1 - beta_b) g^2 (1 - beta formed in float32),
+ * p -= lr_t m / (sqrt(v) + 1e-8), lr_t = lr sqrt(1 - beta_b^t) / (1 - beta_a^t).  The moments and t are the handle's own
+ * (dg_clf_adam_reset, dg_clf_get_adam).  cost [3] (may be NULL) = the step's cost, w, P before the update. */
+int dg_critic_step(dg_clf* h, const float* real, const float* fake, const float* alpha, int B, float gp_lambda,
+                   int penalty_axes, float learning_rate, float beta_a, float beta_b, float* cost, void* stream);
 
 /*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
