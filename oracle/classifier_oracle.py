@@ -38,7 +38,7 @@ def conv2d(x: np.ndarray, K: np.ndarray, b: np.ndarray, strides, padding: str) -
 
 
 def forward(layers, params, x: np.ndarray):
-    """layers: list of ("conv", cout, (kh,kw), (sh,sw), padding) | ("relu",) | ("flatten",) | ("linear", n) | ("softmax",) |
+    """layers: list of ("conv", cout, (kh,kw), (sh,sw), padding) | ("relu",) | ("leakyrelu",) | ("flatten",) | ("linear", n) | ("softmax",) |
     ("dropout",); params: one (W, b) per conv/linear.  Returns (logits, probs)."""
     h = x
     it = iter(params)
@@ -53,6 +53,8 @@ def forward(layers, params, x: np.ndarray):
             h = h @ W.astype(h.dtype) + b.astype(h.dtype)
         elif kind == "relu":
             h = np.maximum(h, 0)
+        elif kind == "leakyrelu":
+            h = np.where(h > 0, h, 0.2 * h)
         elif kind == "flatten":
             h = h.reshape(len(h), -1)
         elif kind == "softmax":
@@ -104,6 +106,8 @@ def input_gradient(layers, params, x: np.ndarray, labels=None):
             W, b = next(it); used.append((W, b)); h = h @ W.astype(h.dtype) + b.astype(h.dtype)
         elif kind == "relu":
             h = np.maximum(h, 0)
+        elif kind == "leakyrelu":
+            h = np.where(h > 0, h, 0.2 * h)
         elif kind == "flatten":
             h = h.reshape(len(h), -1)
         elif kind == "softmax":
@@ -127,6 +131,8 @@ def input_gradient(layers, params, x: np.ndarray, labels=None):
             g = g @ used[pi][0].astype(g.dtype).T
         elif kind == "relu":
             g = g * (out > 0)
+        elif kind == "leakyrelu":
+            g = g * np.where(out > 0, 1.0, 0.2)          # the tie at 0 takes 0.2 (TF's MaximumGrad)
         elif kind == "flatten":
             g = g.reshape(xin.shape)
     return g

@@ -101,7 +101,7 @@ def step_masks(layers, input_shape, B, seed, step, pass_):
 def logits(layers, params, x, masks=None, pre=None):
     """x [B,H,W,C] float64 tensor (NHWC) -> logits (the Softmax layer's input).  ``params``: list of (W, b) float64 tensors.
     ``masks``: {layer: [B, features] array} for the training phase (Dropout y = (x / keep) * mask); None: evaluation.
-    ``pre``: a list that receives every ReLU layer's input."""
+    ``pre``: a list that receives every ReLU / LeakyReLU layer's input."""
     h = x
     it = iter(params)
     for j, L in enumerate(layers):
@@ -122,6 +122,10 @@ def logits(layers, params, x, masks=None, pre=None):
             if pre is not None:
                 pre.append(h)
             h = torch.relu(h)
+        elif kind == "leakyrelu":
+            if pre is not None:
+                pre.append(h)
+            h = torch.where(h > 0, h, 0.2 * h)            # the tie at 0 takes the slope 0.2, as TF's MaximumGrad decides it
         elif kind == "flatten":
             h = h.reshape(h.shape[0], -1)
         elif kind == "dropout":

@@ -14,77 +14,9 @@ from defensegan_amd import _native, critic as K
 from defensegan_amd import network_builder as nb
 from defensegan_amd import utils_tf
 from tests.support import critic_reference as R
+from tests.support.critic_cases import _check_all, _check_grads, _check_terms, _critic, _draw, _safe  # noqa: F401  (shared with test_gpu_critic_shapes.py)
 
 pytestmark = pytest.mark.gpu
-
-
-def _critic(net_dim=8, seed=0, small=False):
-    """mnist_discriminator, or (small) a two-convolution critic on 9 x 6 x 2 inputs: 9x6 -> 5x3 -> 3x2, odd sizes on both axes."""
-    if small:
-        layers = [nb.Conv2D(4, (5, 5), (2, 2), "SAME"), nb.LeakyReLU(), nb.Conv2D(6, (5, 5), (2, 2), "SAME"), nb.LeakyReLU(),
-                  nb.Flatten(), nb.Linear(1)]
-        c = K.Critic(layers, (None, 9, 6, 2), [("D.1.Filters", "D.1.Biases"), ("D.2.Filters", "D.2.Biases"), ("D.Output.W", "D.Output.b")])
-    else:
-        c = K.mnist_discriminator(net_dim=net_dim)
-    w = c.tflib_init(seed)
-    rs = np.random.RandomState(seed + 1)
-    for _, bn in c.param_names:                       # non-zero biases: the bias gradients and the bias-free tangent pass both show
-        w[bn] = rs.uniform(-0.1, 0.1, w[bn].shape).astype(np.float32)
-    c.set_named_weights(w)
-    return c, [(w[a], w[b]) for a, b in c.param_names]
-
-
-def _draw(shape, B, seed):
-    """real: dark images (uniform cubed, mean 1/4); fake: uniform noise (mean 1/2).  Two batches of ONE distribution would make
-    w = mean D(fake) - mean D(real) almost pure cancellation, and a relative bound on it a bound on nothing (_check_terms)."""
-    rs = np.random.RandomState(seed)
-    real = (rs.uniform(0, 1, (B,) + shape) ** 3).astype(np.float32)
-    fake = rs.uniform(0, 1, (B,) + shape).astype(np.float32)
-    return real, fake, rs.uniform(0, 1, B).astype(np.float32)
-
-
-def _safe(c, params, B, seed, lam=10.0, axes=(0, 1), change=lambda batch: batch):
-    """The first of the draws seed, seed + 1000, ... (each passed through ``change``) that the float64 reference alone calls well
-    posed: every LeakyReLU input 1e-6 from zero, and neither w nor the cost more than nine tenths cancellation (conditioning <= 10),
-    so that the relative bounds on them bound the arithmetic and not the luck of the draw."""
-    shape = tuple(c.input_shape[1:])
-    batch, _ = R.safe_batch(R.describe(c), params, lambda a: change(_draw(shape, B, seed + 1000 * a)), max_condition=10.0, lam=lam, axes=axes)
-    return batch
-
-
-def _check_grads(dev, ref, B, bound=1e-4, what="", bias_scales=None):
-    """tests/test_gpu_train.py's form.  One tensor is identically zero in exact arithmetic, the output layer's bias gradient
-    sum_b (+1/B) + sum_b (-1/B): a bound relative to its largest entry says nothing there, so it gets the rounding of a float32 sum
-    of 2 B terms whose partial sums stay within 1, 2 B 2^-24.  ``bias_scales``: where real == fake EVERY bias gradient is the sum
-    of two halves that cancel exactly; each is then bounded relative to the largest entry of one half (given here), which is what
-    the bound means for the two sums the device adds."""
-    for i, ((dW, db), (rW, rb)) in enumerate(zip(dev, ref)):
-        for name, d, r in (("W", dW, rW), ("b", db, rb)):
-            scale, err = np.abs(r).max(), np.abs(d - r).max()
-            if bias_scales is not None and name == "b":
-                scale = bias_scales[i]
-            floor = 2 * B * 2.0 ** -24 if (i == len(dev) - 1 and name == "b") else 1e-12
-            print("%s layer %d d%s: max|dev - ref| = %.3g, max|ref| = %.3g" % (what, i, name, err, scale))
-            assert err <= bound * scale + floor, "%s layer %d d%s: max|dev - ref| = %g, max|ref| = %g" % (what, i, name, err, scale)
-
-
-def _check_terms(dev, ref, what=""):
-    """1e-5 relative on each term (tests/test_gpu_train.py's bound on a loss); the inputs come from _safe, which keeps w and the
-    cost from being mostly cancellation."""
-    for name, d, r in zip(("cost", "w", "P"), dev, ref):
-        print("%s %s: dev %.9g ref %.9g" % (what, name, d, r))
-        assert abs(d - r) <= 1e-5 * abs(r), (what, name, d, r)
-
-
-def _check_all(c, params, batch, lam=10.0, axes=0, what="", bias_scales=None):
-    cost, grads, slopes = c.gradient(*batch, gp_lambda=lam, penalty_axes=axes)
-    terms, rg, rs = R.param_gradient(R.describe(c), params, *batch, lam=lam, axes=axes)
-    assert slopes.shape == rs.shape
-    print("%s slopes: max|dev - ref| = %.3g, max|ref| = %.3g" % (what, np.abs(slopes - rs).max(), np.abs(rs).max()))
-    assert np.abs(slopes - rs).max() <= 1e-4 * np.abs(rs).max()
-    _check_terms(cost, terms, what)
-    _check_grads(grads, rg, len(batch[2]), what=what, bias_scales=bias_scales)
-    return cost, grads, slopes
 
 
 # ---------------------------------------------------------------------- 1. the layer kind
