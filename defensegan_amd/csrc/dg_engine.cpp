@@ -258,6 +258,7 @@ int run_frag(dg_handle* h, GemmOp& op, int d, const float* A, float* Out, bool o
     {
         ProfScope ps(h, s, prof, op.name + sym, 2.0 * (double)op.bplan.macs_per_row * n_rows);
         dg::launch_fgemm(a, s);
+        ++h->frag_launches;
     }
     return launch_check(op.name.c_str());
 }

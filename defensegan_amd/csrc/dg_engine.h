@@ -143,10 +143,12 @@ struct dg_handle {
     std::vector<float*> F, Ft, bias;   // per deconv: [25][cout][cin], [25][cin][cout], [cout]
     std::vector<float*> Fp;            // per non-final deconv: the forward filters in fragment order (dg_fgemm.hip), per tap slab
                                        // [cout / 32][cin / 8][64][4]
-    // The fragment-order forward path (round 6; option frag_path, default on; conditions: frag_active()): F1 writes h1 in fragment
+    // The fragment-order forward path (round 6; option frag_path, default 0 = off; conditions: frag_active()): F1 writes h1 in fragment
     // order + gate bits, every forward deconv runs on dg_fgemm.hip (fragment-order input; output in fragment order, or NHWC for the
     // layer the tail reads), the backward GEMMs take their ReluGrad gates from the bits and write the gradients into the NHWC buffers.
     int frag_path = 0;
+    int64_t frag_launches = 0;         // launches of dg_fgemm.hip made by this handle (dg_debug_read("frag_launches"): tests prove by it
+                                       // that a shape did not quietly stay on dg_gemm.hip)
     const unsigned* tune_gates = nullptr;   // set while prepare_rows times a backward layer's lists: the gate bits it will run with
     std::vector<float*> actf;          // per activation d < nd - 1: fragment-order buffer (rows padded to 32)
     std::vector<unsigned*> gate;       // per activation d < nd - 1: [rows][row_floats / 32] gate bits

@@ -33,6 +33,27 @@ int64_t dg_debug_read(dg_handle* h, const char* what, float* dst, int64_t n) {
             return cnt;
         }
     }
+    else if (w.size() == 4 && w.compare(0, 3, "raw") == 0) {
+        // the NHWC buffer of activation d as it stands, whatever the path: under frag_path it holds the layer's gradient after a
+        // backward pass (and, for every layer but the one the tail reads, nothing the forward wrote)
+        const int d = w[3] - '0';
+        if (d >= 0 && d < (int)h->act.size()) { src = h->act[d]; avail = h->cap_rows * h->act_row[d]; }
+    }
+    else if (w.size() == 5 && w.compare(0, 4, "gate") == 0) {
+        // fragment-order path only: the gate words of activation d, [rows][floats per row / 32] unsigned words viewed as floats
+        const int d = w[4] - '0';
+        if (frag_on(h) && d >= 0 && d < (int)h->gate.size() && h->gate[(size_t)d]) {
+            src = reinterpret_cast<const float*>(h->gate[(size_t)d]);
+            avail = h->cap_rows * (h->act_row[d] / 32);
+        }
+    }
+    else if (w == "frag_launches") {
+        // launches of dg_fgemm.hip this handle has made so far, as one float (exact below 2^24)
+        if (n < 1) return 0;
+        const float v = (float)h->frag_launches;
+        HIP_TRY(hipMemcpy(dst, &v, sizeof(float), hipMemcpyHostToDevice));
+        return 1;
+    }
     else if ((w.size() == 6 && w.compare(0, 5, "bnpre") == 0) || (w.size() == 4 && (w.compare(0, 3, "bnf") == 0 || w.compare(0, 3, "bnb") == 0))) {
         // Batchnorm layer d: the pre-activations its producing GEMM left, its forward / backward statistics [2][bn_C]
         const int d = w.back() - '0';
@@ -117,7 +138,7 @@ static int set_option(dg_handle* h, const char* key, const char* value) {
         drop_job_lists(h);
         return rebuild_plans(h);
     }
-    if (k == "frag_path") {              // 1 = fragment-order forward path (dg_fgemm.hip; default), 0 = every GEMM on dg_gemm.hip
+    if (k == "frag_path") {              // 1 = fragment-order forward path (dg_fgemm.hip), 0 (default) = every GEMM on dg_gemm.hip
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipDeviceSynchronize());
         h->frag_path = atoi(value) < 0 ? 0 : (atoi(value) > 2 ? 2 : atoi(value));       // 2 = persistent waves (dg_fgemm.hip fgemm_persist_kernel)

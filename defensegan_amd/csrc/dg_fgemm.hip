@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "dg_frag_lds.h"
 #include "dg_kernels.h"
 
 namespace dg {
@@ -48,8 +49,8 @@ __device__ __forceinline__ void frag_body(const FragArgs& g, const FragJob jb, c
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ks = PERSIST ? 1 : __builtin_amdgcn_readfirstlane(jb.ksplit);
-    const int q = wave & (ks - 1);                                   // K part of this wave
-    const int tile = PERSIST ? 0 : (ks == 4 ? 0 : (ks == 2 ? wave >> 1 : wave));     // wave tile inside the job
+    const int q = frag_lds::kpart_of(ks, wave);                      // K part of this wave
+    const int tile = PERSIST ? 0 : frag_lds::tile_of(ks, wave);      // wave tile inside the job
     int nvalid = jb.n_mblk - tile * TN;
     nvalid = nvalid > TN ? TN : nvalid;
     const bool active = nvalid > 0;
@@ -176,8 +177,9 @@ __device__ __forceinline__ void frag_body(const FragArgs& g, const FragJob jb, c
     // the reduction and the epilogue are VALU / LDS / store work: beside a co-resident wave's MFMA stream each of their instructions
     // waited for a gap between two MFMAs (profiles/r06_frag_path_ab.txt: 8-13 us per tile); from here on this wave goes first
     __builtin_amdgcn_s_setprio(3);
-    // ---- K-split reduction through LDS: image = [TW][TN][4 quads][64 lanes][4 floats] (b128 per lane: conflict-free)
-    constexpr int IMG_BYTES = TW * TN * 16 * 256;
+    // ---- K-split reduction through LDS: image = [TW][TN][4 quads][64 lanes][4 floats] (b128 per lane: conflict-free).
+    // Where the images and the epilogue slices lie: dg_frag_lds.h (tests/test_frag_lds_cpu.py checks that layout against the
+    // barriers below, transcribed in tests/support/frag_lds_epochs.cpp: a change to either belongs in both)
     auto put = [&](char* img) {
 #pragma unroll
         for (int i = 0; i < TW; ++i)
@@ -204,17 +206,18 @@ __device__ __forceinline__ void frag_body(const FragArgs& g, const FragJob jb, c
     if (dbg & 2) { if (q != 0) { dump(); return; } } else
     if (ks > 1) {
         // round 1: the odd parts hand their accumulators to the even ones (ks = 2: one image per tile; ks = 4: q1 -> q0, q3 -> q2)
-        char* const img1 = smem + (ks == 4 ? (q >> 1) : tile) * IMG_BYTES;
+        char* const img1 = smem + frag_lds::image_off(ks, q, tile, TW, TN);
         if ((q & 1) && active) put(img1);
         __syncthreads();
         if (q & 1) { dump(); return; }
         if (active) add(img1);
         if (ks == 4) {                             // round 2: (q0 + q1) + (q2 + q3)
+            char* const img2 = smem + frag_lds::image2_off();
             __syncthreads();
-            if (q == 2) put(smem);
+            if (q == 2) put(img2);
             __syncthreads();
             if (q == 2) { dump(); return; }
-            add(smem);
+            add(img2);
         }
     }
     if (tron) tr[3] = (long long)__builtin_readcyclecounter();
@@ -234,9 +237,12 @@ __device__ __forceinline__ void frag_body(const FragArgs& g, const FragJob jb, c
         }
     // NHWC output: the tile of one M block (32 rows x 64 channels) is transposed through this wave's own LDS slice (row pitch
     // 272 B: the 16 lanes of a b128 write pass hit 16 different bank quads) so that 16 lanes store the 256 contiguous bytes of one
-    // row -- full 128-B lines; 16-B pieces scattered over 32 rows cost the single epilogue wave 13 us per tile (profiles/r06_frag_path_ab.txt)
-    constexpr int TPITCH = 32 * TW * 4 + 16;
-    char* const tslice = smem + wave * (32 * TPITCH);
+    // row -- full 128-B lines; 16-B pieces scattered over 32 rows cost the single epilogue wave 13 us per tile (profiles/r06_frag_path_ab.txt).
+    // No barrier stands between the reduction and here, so the slice must be bytes no other wave still touches: for ks = 2 it lies
+    // inside this tile's own image, which only this wave reads and has finished reading (slice = wave * 32 * TPITCH put wave 2's
+    // slice into tile 0's image while wave 0 could still be adding it: dg_frag_lds.h)
+    constexpr int TPITCH = frag_lds::slice_pitch(TW);
+    char* const tslice = smem + frag_lds::slice_off(ks, wave, TW, TN);
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         if (j >= nvalid) break;
@@ -312,7 +318,9 @@ __global__ __launch_bounds__(256, 2) void fgemm_persist_kernel(FragArgs g) {
 template <int MODE, bool OUTFRAG>
 void launch_mo(const FragArgs& a, hipStream_t s) {
     constexpr int TW = 2, TN = 4;
-    const int lds = 2 * TW * TN * 16 * 256;
+    constexpr int lds = frag_lds::launch_bytes(TW, TN);
+    static_assert(frag_lds::fits(TW, TN), "an accumulator image or an epilogue slice leaves the launch's dynamic LDS");
+    static_assert(2 * lds <= 160 * 1024, "two workgroups per CU (__launch_bounds__(256, 2)) share 160 KB of LDS");
     if (a.wave_begin) {
         static PerDeviceOnce attrp;
         if (attrp.need())

@@ -159,6 +159,10 @@ int dg_profile_reset(dg_handle* h);
 /* Copies an internal activation buffer of the last forward ("h1","h2","h3","h5" ...) to `dst`
  * (device pointer, capacity n floats); returns the number of floats copied.  Test hook only.
  * Names: "z", "m", "loss", "y", "part", "act<d>" (activation buffer d; after a backward pass it holds that layer's gradient), and
+ * "raw<d>" (the NHWC buffer of activation d as it stands: with the option frag_path "act<d>" always returns the forward activation,
+ * converted from fragment order, and the gradient a backward pass left is read through "raw<d>"), "gate<d>" (frag_path only: the
+ * ReluGrad gate words of activation d, [rows][floats per row / 32] unsigned words viewed as floats, bit f % 32 of word f / 32 =
+ * activation f > 0), "frag_launches" (one float: launches of the fragment-order GEMM this handle has made), and
  * with use_bn, for the Batchnorm layer behind activation d:
  *   "bnpre<d>"  the pre-activations the producing GEMM left ([rows][floats per row of act<d>])
  *   "bnf<d>"    [2][bn_C] forward statistics: mean, rstd = 1 / sqrt(biased variance + 1e-5)

@@ -301,4 +301,15 @@ int dgp2_frag_apply(void* h, int n_rows, int n_wgs, const double* A, const doubl
     return (int)jobs.size();
 }
 
+// Per job of build_frag_jobs: ksplit, n_mblk, n_taps.  Returns the number of jobs, 0 when the layer is not supported (the engine
+// then keeps dg_gemm.hip), -1 when `cap` jobs do not hold the list.
+int dgp2_frag_jobs(void* h, int n_rows, int* out, int cap) {
+    const Batched& b = *static_cast<Batched*>(h);
+    if (!dg::frag_supported(b.plan)) return 0;
+    const std::vector<dg::FragJob> jobs = dg::build_frag_jobs(b.plan, n_rows);
+    if ((int)jobs.size() > cap) return -1;
+    for (size_t i = 0; i < jobs.size(); ++i) { out[3 * i] = jobs[i].ksplit; out[3 * i + 1] = jobs[i].n_mblk; out[3 * i + 2] = jobs[i].n_taps; }
+    return (int)jobs.size();
+}
+
 }  // extern "C"

@@ -1,5 +1,5 @@
-"""-m gpu: the fragment-order forward path (dg_fgemm.hip, option frag_path; default on) against the position-batched
-kernels of dg_gemm.hip (frag_path = 0) and the float64 oracle.
+"""-m gpu: the fragment-order forward path (dg_fgemm.hip, option frag_path; default 0 = off) against the position-batched
+kernels of dg_gemm.hip (frag_path = 0).  The path against float64, layer by layer: tests/test_gpu_frag_values.py.
 
 The two paths compute the same products; the fragment-order kernel splits the K axis of a tile over up to four waves (a fixed
 tree of k-ordered chains per tap class), so the results agree to float32 rounding, not bit for bit; each path is deterministic and
@@ -21,8 +21,15 @@ def _make(arch, frag, R=2, L=3, gain=2.0, seed=1234, lr=10.0):
                                  rec_rr=R, rec_iters=L, rec_lr=lr)
     p = synth.make_weights(arch, seed=seed, gain=gain, bias_range=0.1)
     assert gan.set_weights(p) == []
+    if frag:
+        gan.set_option("two_streams", 0)         # concurrent row groups (CelebA's default: auto) switch the path off
     gan.set_option("frag_path", frag)
     return gan, p
+
+
+def _ran(gan):
+    """dg_fgemm.hip launches this handle has made: a handle that quietly stayed on dg_gemm.hip compares that path with itself."""
+    return int(gan.debug_read("frag_launches", 1).cpu().numpy()[0])
 
 
 def _np(v):
@@ -40,6 +47,7 @@ def test_activations_loss_and_gradient_match_the_position_batched_path(arch, n, 
     z = (rs.standard_normal((n, 128)) * 0.15).astype(np.float32)
     x = rs.uniform(a.in_lo, a.in_hi, size=(n,) + tuple(a.image_dim)).astype(np.float32)
     y1, y0 = _np(g1.generate(z)), _np(g0.generate(z))
+    assert _ran(g1) > 0 and _ran(g0) == 0
     sizes = {"mnist": [4096, 7 * 7 * 128, 14 * 14 * 64], "celeba": [4096, 8 * 8 * 128, 16 * 16 * 64, 32 * 32 * 64]}[arch]
     for d, sz in enumerate(sizes):
         a1 = _np(g1.debug_read("act%d" % d, n * sz)).reshape(n, sz)
@@ -74,6 +82,7 @@ def test_projection_matches_and_rows_are_batch_independent(arch, B, R, frag):
     z0 = synth.make_z(B * R, 128, seed=7)
     d1 = {k: _np(v) for k, v in g1.reconstruct(x, z_init_val=z0, return_details=True).items()}
     d0 = {k: _np(v) for k, v in g0.reconstruct(x, z_init_val=z0, return_details=True).items()}
+    assert _ran(g1) > 0 and _ran(g0) == 0
     np.testing.assert_allclose(d1["loss"], d0["loss"], rtol=2e-4)
     # (three GD steps on adversarial targets amplify the rounding; CelebA's tanh images span [-1, 1] and its loop is the touchier one)
     assert np.abs(d1["rec"] - d0["rec"]).max() < (3e-3 if arch == "mnist" else 3e-2)

@@ -1,7 +1,9 @@
 """tests/support/path_reference.py (the float64 reference and the checks of tests/test_gpu_path_values.py) without a GPU:
 the teacher-forced pieces chain to the NumPy oracle, the tap classes partition every layer and agree with what tests/test_plan.py
 asserts for the planner, and the checks accept a float32 emulation of the path and reject it with one seeded defect at a time --
-each defect by the check, the layer and the tap class it was seeded in."""
+each defect by the check, the layer and the tap class it was seeded in.  Two of the defects are the fragment-order path's own
+(tests/test_gpu_frag_values.py): gate bits read from the neighbouring 32-channel word, and a K-split partial sum replaced by
+another tile's stored outputs (the LDS overlap of DESIGN.md section 4.5)."""
 import numpy as np
 import pytest
 
@@ -129,7 +131,13 @@ def emulate(p, arch, z, x, R, defect=(), stale=None, x_prev=None):
       ("stale_fwd", d, c)  forward layer d: the last (rows * positions) % 32 rows of class c keep the contents of `stale`
       ("stale_bwd", d, c)  the backward that writes grad<d>: ... keep the forward activation (the backward works in place)
       ("gate", d, n)       the backward that writes grad<d> masks row n with row n + 1's gate
-      ("only_prev_x",)     the dz-only call differentiates against x_prev"""
+      ("only_prev_x",)     the dz-only call differentiates against x_prev
+      ("gate_word", d)     the backward that writes grad<d> takes the gate bits of every 32-channel word from the NEXT word of the
+                           row (feature f masked by the gate of feature f + 32): a wrong word index into the fragment-order
+                           path's gate bits
+      ("overlap", d, c)    forward layer d (K = 128: a K split of 2): at one position of class c, channels 32 .. 63, the second
+                           K part's partial sum is replaced by the STORED OUTPUTS (bias and ReLU applied) of another wave tile --
+                           what dg_fgemm.hip's wave 0 summed when wave 2's epilogue slice lay inside tile 0's image"""
     f32 = np.float32
     layers = O._arch_layers(arch)
     nd = PR.n_act(arch)
@@ -148,6 +156,21 @@ def emulate(p, arch, z, x, R, defect=(), stale=None, x_prev=None):
             c = classes[defect[2]]
             sel = mask == defect[2]
             pre[:, sel] -= O.deconv2d(prev, _one_tap(F, [(c["kh"][-1], c["kw"][-1])]), None, h_used)[:, sel]
+        if kind == "overlap" and defect[1] == d:
+            mask, classes = PR.tap_class_masks(arch, d, "fwd")
+            c = classes[defect[2]]
+            taps = [(kh, kw) for kh in c["kh"] for kw in c["kw"]]
+            cin = F.shape[3]
+            half = len(taps) * cin // 2                      # K part 0: the first half of the flattened (tap, k) sequence
+            G = np.zeros_like(F)
+            for t, (kh, kw) in enumerate(taps):
+                n = min(max(half - t * cin, 0), cin)
+                G[kh, kw, :, :n] = F[kh, kw, :, :n]
+            part0 = O.deconv2d(prev, G, None, h_used)
+            pos = np.argwhere(mask == defect[2])
+            (i, j), (i2, j2) = pos[0], pos[-1]               # the hit position and one of another tile
+            other = np.maximum(pre[:, i2, j2, 0:32], 0)      # that tile's stored outputs
+            pre[:, i, j, 32:64] = part0[:, i, j, 32:64] + other + W(name + ".Biases")[32:64]
         return pre
 
     def bwd_layer(d, g_next, gate):
@@ -166,6 +189,8 @@ def emulate(p, arch, z, x, R, defect=(), stale=None, x_prev=None):
             gate = gate.copy()
             if kind == "gate" and defect[1] == d:
                 gate[defect[2]] = gate[defect[2] + 1]
+            if kind == "gate_word" and defect[1] == d:
+                gate = np.roll(gate.reshape(len(gate), -1), -32, axis=1).reshape(gate.shape)
             g = g * gate
         return g
 
@@ -242,7 +267,12 @@ def _cases():
         out.append((arch, ("stale_bwd", 1, 0), 3, "grad1 class %d"))
         out.append((arch, ("gate", 1, 1), 3, None))
         out.append((arch, ("only_prev_x",), 5, None))
+        out.append((arch, ("gate_word", 1), 3, None))
     out.append(("mnist", ("kpair", 1, 0), 3, "grad1 class %d"))                       # 7x7 <- 14x14: 25 positions x 25 taps
+    # the K = 128 layers the fragment-order path splits in two: MNIST's writes act2 as NHWC rows (where the overlap was), CelebA's
+    # writes fragment order
+    out.append(("mnist", ("overlap", 2, 0), 1, "act2 class %d"))
+    out.append(("celeba", ("overlap", 2, 1), 1, "act2 class %d"))
     return out
 
 
@@ -254,8 +284,8 @@ def test_checks_reject_one_seeded_defect(arch, defect, check, label):
     got = res.labels(check)
     print("\n  " + "\n  ".join(l for _, _, l in res.fails))
     assert got, "defect %s was not rejected by check (%d)" % (defect, check)
-    if defect[0] == "gate":
-        # one row of grad<d> is masked wrongly: the layer's own teacher-forced check fails, the layers behind it (computed from what
+    if defect[0] in ("gate", "gate_word"):
+        # one row of grad<d> (gate_word: every row) is masked wrongly: the layer's own teacher-forced check fails, the layers behind it (computed from what
         # the record holds) do not
         assert {l.split(" class")[0] for l in got} == {"grad%d" % defect[1]}
     elif defect[0] == "only_prev_x":
