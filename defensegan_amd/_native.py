@@ -74,6 +74,12 @@ SYMBOLS = [
     ("dg_row_norms", _i, [_vp, _vp, _i, _i64, _i, _vp, _vp]),
     ("dg_critic_gradient", _i, [_vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
     ("dg_critic_step", _i, [_vp, _vp, _vp, _vp, _i, _f, _i, _f, _f, _f, _vp, _vp]),
+    ("dg_gen_param_gradient", _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("dg_gen_step", _i, [_vp, _vp, _vp, _i, _f, _f, _f, _vp]),
+    ("dg_get_weights", _i, [_vp, _cp, _vp, _i]),
+    ("dg_gen_adam_reset", _i, [_vp]),
+    ("dg_gen_get_adam", _i, [_vp, _cp, _vp, _vp, C.POINTER(_i64), _i]),
+    ("dg_gen_set_adam", _i, [_vp, _cp, _vp, _vp, _i64, _i]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

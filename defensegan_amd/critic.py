@@ -8,7 +8,7 @@
 
 The container is network_builder.MLP with one more layer kind; the arithmetic is the HIP library's (csrc/dg_critic.hip).  Parameters
 carry tflib's names, so that a weight pack (.npz) or -- through tf_checkpoint -- a reference checkpoint fills them.  A Batchnorm
-critic (USE_BN: True) and the CelebA critic are not implemented.
+critic (USE_BN: True) and the CelebA critic are not implemented.  The generator's half of the loop is gan.train_gan / generator_step.
 """
 from __future__ import annotations
 

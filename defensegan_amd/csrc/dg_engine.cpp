@@ -263,6 +263,14 @@ int run_frag(dg_handle* h, GemmOp& op, int d, const float* A, float* Out, bool o
     return launch_check(op.name.c_str());
 }
 
+// the shapes for which build_lin_packs makes the forward / the backward pack
+bool lin_pack_fwd_shapes(const dg_handle* h) {
+    return h->lin_out % 128 == 0 && h->latent % 32 == 0 && dg::lin_stationary_supported(h->latent / 32, dg::EPI_BIAS_RELU);
+}
+bool lin_pack_bwd_shapes(const dg_handle* h) {
+    return h->latent == 128 && h->lin_out % (h->nsplit * 32) == 0 && dg::lin_stationary_supported(h->lin_out / h->nsplit / 32, dg::EPI_STORE);
+}
+
 // Fragment-order copies of the Linear weights for dg_linear.hip (forward: 128-feature column tiles of W^T; backward: the
 // nsplit K slices of W, all 128 latent columns each), built from the host copy kept by dg_set_weights.
 int build_lin_packs(dg_handle* h) {
@@ -270,45 +278,25 @@ int build_lin_packs(dg_handle* h) {
     HIP_TRY(hipDeviceSynchronize());
     fr(h->lin_pack_fwd); fr(h->lin_pack_bwd);
     ++h->list_epoch;
+    ++h->pack_epoch;                 // the gather maps of the training step (dg_gen_train.hip) describe the packs freed above
     if (h->lin_w_host.empty()) return DG_OK;
     const int K = h->latent, F = h->lin_out;
+    // (after a training step the device holds the weights: the host copy follows before it is packed again)
+    if (h->lin_w_trained) HIP_TRY(hipMemcpy(h->lin_w_host.data(), h->lin_w, (size_t)K * F * sizeof(float), hipMemcpyDeviceToHost));
     const float* W = h->lin_w_host.data();               // [K][F]
     std::vector<float> pk((size_t)K * F);
-    if (F % 128 == 0 && K % 32 == 0 && dg::lin_stationary_supported(K / 32, dg::EPI_BIAS_RELU)) {
-        const int kch = K / 32;
-        for (int u = 0; u < F / 128; ++u)
-            for (int w = 0; w < 4; ++w)
-                for (int c = 0; c < kch; ++c)
-                    for (int kk = 0; kk < 4; ++kk)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 4; ++e) {
-                                const int f = u * 128 + w * 32 + (lane & 31), k = c * 32 + (kk * 2 + (lane >> 5)) * 4 + e;
-                                pk[(size_t)dg::lin_pack_index(u, w, kch, c, kk, lane, e)] = W[(size_t)k * F + f];      // W^T[f][k]
-                            }
+    if (lin_pack_fwd_shapes(h)) {
+        dg::pack_lin_fwd(W, pk.data(), K, F);
         HIP_TRY(hipMalloc(&h->lin_pack_fwd, pk.size() * sizeof(float)));
         HIP_TRY(hipMemcpy(h->lin_pack_fwd, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    if (K == 128 && F % (h->nsplit * 32) == 0 && dg::lin_stationary_supported(F / h->nsplit / 32, dg::EPI_STORE)) {
-        const int ks = F / h->nsplit, kch = ks / 32;
-        for (int s = 0; s < h->nsplit; ++s)
-            for (int w = 0; w < 4; ++w)
-                for (int c = 0; c < kch; ++c)
-                    for (int kk = 0; kk < 4; ++kk)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 4; ++e) {
-                                const int d = w * 32 + (lane & 31), f = s * ks + c * 32 + (kk * 2 + (lane >> 5)) * 4 + e;
-                                pk[(size_t)dg::lin_pack_index(s, w, kch, c, kk, lane, e)] = W[(size_t)d * F + f];
-                            }
+    if (lin_pack_bwd_shapes(h)) {
+        dg::pack_lin_bwd(W, pk.data(), K, F, h->nsplit);
         HIP_TRY(hipMalloc(&h->lin_pack_bwd, pk.size() * sizeof(float)));
         HIP_TRY(hipMemcpy(h->lin_pack_bwd, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     return DG_OK;
 }
-
-// The momentum update riding in the Linear backward launch: the rows' z / m, their arrival counters and the step's constants.
-struct UpdateFold {
-    float* z; float* m; unsigned* count; float lr, momentum;
-};
 
 int run_lin_stationary(dg_handle* h, GemmOp& op, const float* A, float* Out, int n_rows, hipStream_t s, bool prof,
                        const UpdateFold* uf = nullptr, float* out_frag = nullptr, unsigned* gates = nullptr) {
@@ -383,10 +371,7 @@ int run_gemm(dg_handle* h, GemmOp& op, const float* A, float* Out, int n_rows, h
 // A row group = a contiguous range of latent rows (whole images) processed on one stream.  Rows are independent
 // (use_bn = False), so a batch may be split into groups that run concurrently on two streams: one group's
 // VALU/LDS-bound tail and short kernels then overlap the other group's MFMA-bound GEMMs.
-struct RowGroup {
-    int row0 = 0, n_rows = 0;
-    hipStream_t s = nullptr;
-};
+// (struct RowGroup: dg_engine.h)
 
 // Row groups of a call over B images x R restarts (whole images per group; the streams are assigned by the caller).
 int split_groups(const dg_handle* h, int B, int R, RowGroup* grp, int force = -1);
@@ -530,7 +515,7 @@ dg::BnArgs bn_args(dg_handle* h, const ActInfo& a, int n_rows) {
 // want_loss: the per-row loss is only read after the last step (selection) and by dg_loss_grad; the CelebA tail leaves
 // per-band partial sums, whose reduction is skipped when nobody reads the result.
 int run_forward(dg_handle* h, const float* x, const RowGroup& g, int R, bool want_y, bool want_loss, bool tail_backward, bool prof,
-                bool have_f1 = false) {
+                bool have_f1) {
     const int n_rows = g.n_rows;
     hipStream_t s = g.s;
     const int64_t r0 = g.row0;
@@ -667,7 +652,10 @@ bool update_folds(const dg_handle* h) {
     return h->update_fold && h->upd_count && lin_stationary(h, h->B1) && dg::lin_fold_supported(h->nsplit, h->latent);
 }
 
-int run_backward(dg_handle* h, const RowGroup& g, bool prof, const UpdateFold* uf = nullptr, bool without_b1 = false) {
+// before_layer (the generator's training step, dg_gen_train.hip): called ahead of the launch that overwrites activation d with its
+// gradient -- d = the deconv index for Bd[d], -1 for the Linear backward -- because a layer's weight gradient needs that layer's
+// input activation, which the in-place backward destroys.  Order per layer, top down: weight gradient, then backward-to-input.
+int run_backward(dg_handle* h, const RowGroup& g, bool prof, const UpdateFold* uf, bool without_b1, const std::function<int(int)>* before_layer) {
     const int nd = (int)h->dec.size();
     const int64_t r0 = g.row0;
     // Batchnorm backward of activation k: the sums come from the epilogue of the GEMM that wrote dy (EPI_MASK_STATS) or from a pass
@@ -683,11 +671,14 @@ int run_backward(dg_handle* h, const RowGroup& g, bool prof, const UpdateFold* u
     };
     for (int d = nd - 2; d >= 0; --d) {
         if (h->ai[d + 1].has_bn) bn_backward(d + 1);
-        int rc = run_gemm(h, h->Bd[d], h->act[d + 1] + r0 * h->act_row[d + 1], h->act[d] + r0 * h->act_row[d], g.n_rows, g.s, prof,
+        int rc = before_layer ? (*before_layer)(d) : DG_OK;
+        if (rc) return rc;
+        rc = run_gemm(h, h->Bd[d], h->act[d + 1] + r0 * h->act_row[d + 1], h->act[d] + r0 * h->act_row[d], g.n_rows, g.s, prof,
                           frag_on(h) && r0 == 0 ? h->gate[d] : nullptr);
         if (rc) return rc;
     }
     if (h->ai[0].has_bn) bn_backward(0);
+    if (before_layer) { const int rc = (*before_layer)(-1); if (rc) return rc; }
     if (without_b1) return DG_OK;                    // the fused latent turn follows (run_latent_turn)
     if (uf) return run_lin_stationary(h, h->B1, h->act[0] + r0 * h->act_row[0], h->part + r0 * h->nsplit * h->latent, g.n_rows, g.s, prof, uf);
     return run_gemm(h, h->B1, h->act[0] + r0 * h->act_row[0], h->part + r0 * h->nsplit * h->latent, g.n_rows, g.s, prof);
@@ -1026,6 +1017,7 @@ int dg_destroy(dg_handle* h) {
     if (!h) return DG_OK;
     (void)hipSetDevice(h->device);
     prof_collect(h);
+    gen_train_release(h);
     if (h->turn_err_host) { (void)hipHostFree(h->turn_err_host); h->turn_err_host = nullptr; }
     drop_graphs(h);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
@@ -1091,8 +1083,8 @@ int dg_set_weights(dg_handle* h, const char* name, const float* data, const int6
     HIP_TRY(hipMemcpy(host.data(), data, (size_t)n * sizeof(float), is_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
     if (nm == "Generator.Input.W") {
         std::vector<float> t((size_t)n);
-        for (int d = 0; d < h->latent; ++d)
-            for (int f = 0; f < h->lin_out; ++f) t[(size_t)f * h->latent + d] = host[(size_t)d * h->lin_out + f];
+        dg::pack_lin_transpose(host.data(), t.data(), h->latent, h->lin_out);
+        h->lin_w_trained = false;
         HIP_TRY(hipMemcpy(h->lin_w, host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(h->lin_wt, t.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
         h->lin_w_host = host;
@@ -1110,40 +1102,25 @@ int dg_set_weights(dg_handle* h, const char* name, const float* data, const int6
         const DeconvSpec& s = h->dec[d];
         if (nm == std::string(s.name) + ".Filters") {
             std::vector<float> t((size_t)n);
-            for (int k = 0; k < 25; ++k)
-                for (int co = 0; co < s.cout; ++co)
-                    for (int ci = 0; ci < s.cin; ++ci)
-                        t[((size_t)k * s.cin + ci) * s.cout + co] = host[((size_t)k * s.cout + co) * s.cin + ci];
+            dg::pack_deconv_transpose(host.data(), t.data(), s.cout, s.cin);
             HIP_TRY(hipMemcpy(h->F[d], host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(h->Ft[d], t.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
             if (d + 1 < h->dec.size() && s.cout % 32 == 0 && s.cin % 8 == 0) {
                 // forward filters in fragment order (dg_fgemm.hip): the slab of tap k keeps its float offset k * cout * cin; inside it
                 // [cout / 32][cin / 8][64 lanes][4]: lane = ((ci % 8) / 4) * 32 + co % 32, element ci % 4
                 std::vector<float> pk((size_t)n);
-                const int kc8 = s.cin / 8;
-                for (int k = 0; k < 25; ++k)
-                    for (int co = 0; co < s.cout; ++co)
-                        for (int ci = 0; ci < s.cin; ++ci)
-                            pk[(size_t)k * s.cout * s.cin + (((size_t)(co / 32) * kc8 + ci / 8) * 64 + ((ci % 8) / 4) * 32 + co % 32) * 4 + ci % 4] =
-                                host[((size_t)k * s.cout + co) * s.cin + ci];
-                if (!h->Fp[d]) HIP_TRY(hipMalloc(&h->Fp[d], (size_t)n * sizeof(float)));
+                dg::pack_deconv_frag(host.data(), pk.data(), s.cout, s.cin);
+                if (!h->Fp[d]) { HIP_TRY(hipMalloc(&h->Fp[d], (size_t)n * sizeof(float))); ++h->pack_epoch; }
                 HIP_TRY(hipMemcpy(h->Fp[d], pk.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
             }
             if (d + 1 == h->dec.size()) {
                 // tail forward GEMM: B fragments of v_mfma_f32_32x32x2_f32 in load order.  kappa = (kh*5+kw)*cout + co is
                 // the row of host[] (layout [25][cout][cin] == [kappa][c]); lane = (kappa & 31) + 32*half holds
                 // c = 8*kk + 4*half + e of kappa tile t.
-                const int nk = 25 * s.cout, nt = (nk + 31) / 32, kkn = s.cin / 8;
-                std::vector<float> pk((size_t)nt * kkn * 64 * 4, 0.f);
-                for (int tt = 0; tt < nt; ++tt)
-                    for (int kk = 0; kk < kkn; ++kk)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 4; ++e) {
-                                const int kappa = tt * 32 + (lane & 31), c = kk * 8 + (lane >> 5) * 4 + e;
-                                if (kappa < nk) pk[(((size_t)tt * kkn + kk) * 64 + lane) * 4 + e] = host[(size_t)kappa * s.cin + c];
-                            }
+                std::vector<float> pk(dg::tail_pack32_elems(s.cout, s.cin), 0.f);
+                dg::pack_tail32(host.data(), pk.data(), s.cout, s.cin);
 #ifdef DG_MEASURE      // only the superseded 32-wide CelebA forward tail reads this pack
-                if (!h->tail_pack) HIP_TRY(hipMalloc(&h->tail_pack, pk.size() * sizeof(float)));
+                if (!h->tail_pack) { HIP_TRY(hipMalloc(&h->tail_pack, pk.size() * sizeof(float))); ++h->pack_epoch; }
                 HIP_TRY(hipMemcpy(h->tail_pack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
 #else
                 (void)pk;
@@ -1151,16 +1128,9 @@ int dg_set_weights(dg_handle* h, const char* name, const float* data, const int6
                 if (s.cout == 3) {
                     // B fragments of v_mfma_f32_16x16x4_f32, one 16-column tile per filter row kh: column
                     // j = kw*3 + co (< 15) is kappa = 15*kh + j; lane = j + 16*g holds c = 16*kk + 4*g + e.
-                    const int kk16 = s.cin / 16;
-                    std::vector<float> p16((size_t)5 * kk16 * 64 * 4, 0.f);
-                    for (int kh = 0; kh < 5; ++kh)
-                        for (int kk = 0; kk < kk16; ++kk)
-                            for (int lane = 0; lane < 64; ++lane)
-                                for (int e = 0; e < 4; ++e) {
-                                    const int j = lane & 15, c = kk * 16 + (lane >> 4) * 4 + e;
-                                    if (j < 15) p16[(((size_t)kh * kk16 + kk) * 64 + lane) * 4 + e] = host[(size_t)(15 * kh + j) * s.cin + c];
-                                }
-                    if (!h->tail_pack16) HIP_TRY(hipMalloc(&h->tail_pack16, p16.size() * sizeof(float)));
+                    std::vector<float> p16(dg::tail_pack16_elems(s.cin), 0.f);
+                    dg::pack_tail16(host.data(), p16.data(), s.cin);
+                    if (!h->tail_pack16) { HIP_TRY(hipMalloc(&h->tail_pack16, p16.size() * sizeof(float))); ++h->pack_epoch; }
                     HIP_TRY(hipMemcpy(h->tail_pack16, p16.data(), p16.size() * sizeof(float), hipMemcpyHostToDevice));
                 }
             }

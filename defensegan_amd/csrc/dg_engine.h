@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <queue>
 #include <string>
@@ -140,6 +141,12 @@ struct dg_handle {
     float* lin_pack_fwd = nullptr; // lin_wt / lin_w in the MFMA fragment order of dg_linear.hip (dg_kernels.h lin_pack_index), or nullptr
     float* lin_pack_bwd = nullptr;
     std::vector<float> lin_w_host; // [latent][lin_out]: the packs are rebuilt when nsplit changes
+    bool lin_w_trained = false;    // a training step has moved lin_w on the device since lin_w_host was filled (build_lin_packs fetches it)
+    // The parameters in the reference layouts -- lin_w, lin_b, F[d], bias[d] -- are the MASTER COPY that the generator's training step
+    // (dg_gen_train.hip) updates; every other weight buffer is derived from them by a packer of dg_pack.h and refreshed on the device
+    // through that packer's gather map.  pack_epoch counts the (re)allocations of derived buffers: maps of an older epoch are rebuilt.
+    uint64_t pack_epoch = 0;
+    struct GenTrain* gen_train = nullptr;   // workspace, Adam state and gather maps of the training step (dg_gen_train.hip), or nullptr
     std::vector<float*> F, Ft, bias;   // per deconv: [25][cout][cin], [25][cin][cout], [cout]
     std::vector<float*> Fp;            // per non-final deconv: the forward filters in fragment order (dg_fgemm.hip), per tap slab
                                        // [cout / 32][cin / 8][64][4]
@@ -333,6 +340,26 @@ const JobList* get_jobs(dg_handle* h, GemmOp& op, int n_rows, const float* A, fl
 const FragList* find_frag_jobs(const GemmOp& op, int n_rows);
 const FragList* get_frag_jobs(GemmOp& op, int n_rows, int persist_wgs = 0);
 // ---- dg_engine.cpp
+// A row group = a contiguous range of latent rows (whole images) processed on one stream.
+struct RowGroup {
+    int row0 = 0, n_rows = 0;
+    hipStream_t s = nullptr;
+};
+// The momentum update riding in the Linear backward launch: the rows' z / m, their arrival counters and the step's constants.
+struct UpdateFold {
+    float* z; float* m; unsigned* count; float lr, momentum;
+};
+int prepare_rows(dg_handle* h, int64_t cap_rows, const int* rows, int n, hipStream_t s);
+int run_forward(dg_handle* h, const float* x, const RowGroup& g, int R, bool want_y, bool want_loss, bool tail_backward, bool prof,
+                bool have_f1 = false);
+int run_backward(dg_handle* h, const RowGroup& g, bool prof, const UpdateFold* uf = nullptr, bool without_b1 = false,
+                 const std::function<int(int)>* before_layer = nullptr);
+int check_rows(int B, int R, int* n_rows);
+int check_ready(dg_handle* h);
+bool lin_pack_fwd_shapes(const dg_handle* h);
+bool lin_pack_bwd_shapes(const dg_handle* h);
+// ---- dg_gen_train.hip
+void gen_train_release(dg_handle* h);
 bool lin_stationary(const dg_handle* h, const GemmOp& op);
 bool frag_on(const dg_handle* h);
 int build_lin_packs(dg_handle* h);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dg_types.h"
+#include "dg_pack.h"
 
 namespace dg {
 
@@ -170,11 +171,7 @@ struct LinArgs {
 };
 bool lin_stationary_supported(int kch, int mode);
 bool lin_fold_supported(int units, int latent);
-// float index inside Wp of element e of the fragment (unit, wave, chunk c, k-step kk, lane): the weight of output column
-// wave*32 + (lane & 31) of the unit at k = c*32 + (kk*2 + (lane >> 5))*4 + e
-__host__ __device__ inline long long lin_pack_index(int unit, int wave, int kch, int c, int kk, int lane, int e) {
-    return ((((long long)(unit * 4 + wave) * kch + c) * 4 + kk) * 64 + lane) * 4 + e;
-}
+// float index inside Wp of element e of the fragment (unit, wave, chunk c, k-step kk, lane): lin_pack_index, dg_pack.h
 void launch_lin_stationary(const LinArgs& a, hipStream_t s);
 
 // ---- the latent turn as one launch (dg_turn.hip; engine option turn_fused) ----------------------

@@ -580,7 +580,7 @@ class DefenseGANBase(object):
         ``batch_size`` of ``images`` [n,H,W,C] (generator range), in the order of ``critic_schedule``.  Step k takes the fake batch
         and alpha of ``_critic_inputs(batch_size, k, seed, gen)``, gen one device generator seeded with ``seed``.  Nothing waits for
         the device inside the loop.  Returns [train_iters, 3]: each iteration's last cost, w and P (the reference plots the first).
-        ``phase=None`` asks for generator steps as well, which are not implemented."""
+        ``phase=None`` asks for generator steps as well: that loop is ``train_gan``; this entry keeps raising for it."""
         self._check_mode()
         if phase is None:
             raise NotImplementedError("train(phase=None) needs the generator step (a generator backward seeded from the critic, with "
@@ -645,6 +645,197 @@ class DefenseGANBase(object):
             _native.check(lib.dg_clf_set_adam(c._handle, c._native_index[li], m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p),
                                               int(have["adam_t"]), 0))
 
+    # ------------------------------------------------------------------ the generator step (gan.py:167-199, 273-293)
+    def _check_trainable(self):
+        """What the generator's training step is built for: MODE wgan-gp, the MNIST / F-MNIST generator, USE_BN False."""
+        self._check_mode()
+        if self._arch.arch_id == archs.ARCH_CELEBA:
+            raise NotImplementedError("training the CelebA generator is not implemented: only the MNIST / F-MNIST generator is")
+        if self.use_bn:
+            raise NotImplementedError("training a Batchnorm generator (USE_BN: True) is not implemented")
+
+    def weight_names(self):
+        return list(archs.weight_shapes(self._arch, bool(self.use_bn)))
+
+    def get_weights(self) -> Dict[str, np.ndarray]:
+        """{tflib name: array in the reference layout}: the handle's current parameters (dg_get_weights), which training moves on
+        the device; Batchnorm scale / offset, which nothing moves, as they were set."""
+        self._ensure_handle()
+        if not self.initialized:
+            raise _native.NativeError("generator weights not loaded (load_generator / set_weights)")
+        lib = self._lib()
+        out = {}
+        for name, shape in archs.weight_shapes(self._arch, bool(self.use_bn)).items():
+            if ".BN" in name:
+                out[name] = self._weights[name].copy()
+                continue
+            a = np.empty(shape, np.float32)
+            self._check(lib.dg_get_weights(self._handle, name.encode(), a.ctypes.data_as(C.c_void_p), 0))
+            out[name] = a
+        return out
+
+    def split_grads(self, flat) -> Dict[str, np.ndarray]:
+        """dg_gen_param_gradient's flat gradient as {name: array}, in the order of archs.weight_shapes(arch, use_bn=False)."""
+        out, off = {}, 0
+        for name, shape in archs.weight_shapes(self._arch, False).items():
+            n = int(np.prod(shape))
+            out[name] = flat[off:off + n].reshape(shape)
+            off += n
+        return out
+
+    def n_params(self) -> int:
+        return sum(int(np.prod(s)) for s in archs.weight_shapes(self._arch, False).values())
+
+    def _critic_seed(self, y):
+        """(cost, dy) on the device for y = G(z) [B,H,W,C]: cost = -mean D(y) (gan.py:168) and dy = d cost / dy, the critic's input
+        gradient for dlogits = -1/B (dg_clf_backward).  The critic's weights do not move."""
+        torch = _torch()
+        self.critic._device = self._device
+        B = int(y.shape[0])
+        cost = -self.critic.discriminate(y).mean()
+        dl = torch.full((B, 1), -1.0 / B, dtype=torch.float32, device=y.device)
+        return cost, self.critic.backward(y, dl)
+
+    def generator_cost(self, z) -> float:
+        """The reference's ``generator_cost`` fetch: -mean D(G(z)) (gan.py:168)."""
+        self._check_trainable()
+        self._ensure_handle()
+        cost, _ = self._critic_seed(self.generate(self._to_device(z)))
+        return float(cost.cpu())
+
+    def _gen_inputs(self, z, dy):
+        self._check_trainable()
+        self._ensure_handle()
+        if not self.initialized:
+            raise _native.NativeError("generator weights not loaded (load_generator / set_weights)")
+        zz = self._to_device(z)
+        if zz.dim() != 2 or int(zz.shape[1]) != int(self.latent_dim) or int(zz.shape[0]) < 1:
+            raise ValueError("z must be [N,%d] with N >= 1, got %r" % (int(self.latent_dim), tuple(zz.shape)))
+        N = int(zz.shape[0])
+        cost = None
+        if dy is None:
+            cost, dy = self._critic_seed(self.generate(zz))
+        dy = self._to_device(dy)
+        if int(dy.numel()) != N * self._arch.pixels:
+            raise ValueError("dy must be [%d,%d,%d,%d], got %r" % ((N,) + tuple(self._arch.image_dim) + (tuple(dy.shape),)))
+        return zz, dy, N, cost
+
+    def generator_gradient(self, z, dy=None, sync=True):
+        """(cost, {name: gradient}, dz) of the generator at ``z`` [N, latent] (dg_gen_param_gradient).  ``dy`` [N,H,W,C] is the
+        gradient with respect to G(z); None means the critic's seed, the composition the reference's ``gen_train_op`` differentiates:
+        cost = -mean D(G(z)), dy = dg_clf_backward on the critic at G(z) with dlogits = -1/N (cost is None for an explicit ``dy``).
+        ``sync``: NumPy results; otherwise (cost tensor, flat gradient tensor, dz tensor) on the device and no wait."""
+        torch = _torch()
+        zz, dy, N, cost = self._gen_inputs(z, dy)
+        grads = torch.empty(self.n_params(), dtype=torch.float32, device=zz.device)
+        dz = torch.empty_like(zz)
+        with torch.cuda.device(zz.device):
+            self._check(self._lib().dg_gen_param_gradient(self._handle, zz.data_ptr(), dy.data_ptr(), N, grads.data_ptr(), None,
+                                                          dz.data_ptr(), torch.cuda.current_stream(zz.device).cuda_stream))
+        if not sync:
+            return cost, grads, dz
+        return (None if cost is None else float(cost.cpu())), self.split_grads(grads.cpu().numpy()), dz.cpu().numpy()
+
+    def generator_step(self, z, dy=None, learning_rate=1e-4, beta1=0.5, beta2=0.9):
+        """One Adam step of the generator (dg_gen_step; the reference's gen_train_op: 1e-4, 0.5, 0.9) on the gradient of
+        ``generator_gradient(z, dy)``; every derived weight layout of the engine follows on the device.  Returns the cost before the
+        update as a device tensor without waiting (None for an explicit ``dy``)."""
+        torch = _torch()
+        zz, dy, N, cost = self._gen_inputs(z, dy)
+        with torch.cuda.device(zz.device):
+            self._check(self._lib().dg_gen_step(self._handle, zz.data_ptr(), dy.data_ptr(), N, float(learning_rate), float(beta1),
+                                                float(beta2), torch.cuda.current_stream(zz.device).cuda_stream))
+        return cost
+
+    def generator_adam_reset(self) -> None:
+        self._check_trainable()
+        self._ensure_handle()
+        self._check(self._lib().dg_gen_adam_reset(self._handle))
+
+    def generator_adam_state(self):
+        """({name: m}, {name: v}, t) of the generator's optimiser (dg_gen_get_adam)."""
+        self._check_trainable()
+        self._ensure_handle()
+        lib = self._lib()
+        m, v, t = {}, {}, C.c_int64(0)
+        for name, shape in archs.weight_shapes(self._arch, False).items():
+            m[name], v[name] = np.empty(shape, np.float32), np.empty(shape, np.float32)
+            self._check(lib.dg_gen_get_adam(self._handle, name.encode(), m[name].ctypes.data_as(C.c_void_p),
+                                            v[name].ctypes.data_as(C.c_void_p), C.byref(t), 0))
+        return m, v, int(t.value)
+
+    def _set_generator_adam(self, m, v, t) -> None:
+        lib = self._lib()
+        for name in archs.weight_shapes(self._arch, False):
+            mm, vv = np.ascontiguousarray(m[name], np.float32), np.ascontiguousarray(v[name], np.float32)
+            self._check(lib.dg_gen_set_adam(self._handle, name.encode(), mm.ctypes.data_as(C.c_void_p), vv.ctypes.data_as(C.c_void_p),
+                                            int(t), 0))
+
+    def save_generator(self, path: str) -> None:
+        """An .npz of the generator: its parameters under their tflib names (what load_generator and --init_path read), Adam's moments
+        as ``adam_m/<name>`` and ``adam_v/<name>`` and the step count ``adam_t`` (what load_generator_state also restores)."""
+        arrays = dict(self.get_weights())
+        m, v, t = self.generator_adam_state()
+        arrays.update(generator_state_arrays(m, v, t))
+        with open(path, "wb") as fh:
+            np.savez(fh, **arrays)
+
+    def load_generator_state(self, path: str) -> None:
+        """load_generator(path) and the optimiser with it: Adam's moments and step count when the .npz holds them (save_generator),
+        a fresh optimiser when not.  (load_generator itself keeps ignoring those keys: it works without a device.)"""
+        self._check_trainable()
+        self.load_generator(path)
+        self._ensure_handle()
+        state = None
+        if path.endswith(".npz") or os.path.isdir(path):
+            p = os.path.join(path, "generator.npz") if os.path.isdir(path) else path
+            if os.path.exists(p):
+                with np.load(p) as f:
+                    state = split_generator_state({k: f[k] for k in f.files}, list(archs.weight_shapes(self._arch, False)))
+        if state is None:
+            self.generator_adam_reset()
+        else:
+            self._set_generator_adam(*state)
+
+    def train_gan(self, images, train_iters=None, seed=None, learning_rate=1e-4, beta1=0.5, beta2=0.9, start_iter=0):
+        """What the reference's ``train(phase=None)`` does (gan.py:273-293): ``train_iters`` iterations, every one after the first
+        starting with ONE generator step (``generator_step`` with the critic's seed) followed by ``critic_iters`` critic steps exactly
+        as ``train(phase="disc")`` schedules them -- the same ``critic_schedule``, ``_critic_inputs`` and alpha stream, k the running
+        critic-step index -- whose fake batches come from the generator's CURRENT weights.  The generator step of iteration ``it``
+        takes z = init_latents(batch_size, seed=seed + 1, first_row=it * batch_size, std=1.0).  Nothing waits for the device inside the
+        loop.  ``start_iter`` continues a run: the iterations [start_iter, start_iter + train_iters) of the run that began at 0 with
+        the same ``seed`` (the schedule and the alpha stream are advanced past the earlier ones; weights and optimisers are the
+        caller's to restore).  Returns [train_iters, 4]: each iteration's last critic cost, w and P, and the cost of its generator step
+        (NaN for iteration 0, which has none)."""
+        self._check_trainable()
+        torch = _torch()
+        self._ensure_handle()
+        if not self.initialized:
+            raise _native.NativeError("generator weights not loaded (load_generator / set_weights)")
+        self.critic._device = self._device
+        iters = int(self.train_iters if train_iters is None else train_iters)
+        ci, bs, first = int(self.critic_iters), int(self.batch_size), int(start_iter)
+        if seed is None:
+            seed = self._default_seed
+        x = self._to_device(images)
+        sched = torch.from_numpy(self.critic_schedule(int(x.shape[0]), (first + iters) * ci, seed)).to(x.device)
+        gen = self._alpha_generator(seed)
+        for _ in range(first * ci):                   # the alphas of the iterations already run
+            torch.rand(bs, generator=gen, device=x.device, dtype=torch.float32)
+        costs = torch.full((iters, 4), float("nan"), dtype=torch.float32, device=x.device)
+        scratch = torch.empty(3, dtype=torch.float32, device=x.device)
+        lam = float(self.gradient_penalty_lambda)
+        for it, k0, gen_step in gan_iteration_plan(first, iters, ci):
+            if gen_step:
+                z = self.init_latents(bs, seed=seed + 1, first_row=it * bs, std=1.0)
+                costs[it - first, 3] = self.generator_step(z, learning_rate=learning_rate, beta1=beta1, beta2=beta2)
+            for i in range(ci):
+                k = k0 + i
+                fake, alpha = self._critic_inputs(bs, k, seed, gen)
+                self.critic.step(x[sched[k]], fake, alpha, gp_lambda=lam, penalty_axes=self.penalty_axes, learning_rate=learning_rate,
+                                 beta1=beta1, beta2=beta2, cost=costs[it - first, :3] if i == ci - 1 else scratch)
+        return costs.cpu().numpy()
+
     # ------------------------------------------------------------------ measurement hooks
     def set_option(self, key: str, value) -> None:
         self._ensure_handle()
@@ -683,6 +874,32 @@ class DefenseGANBase(object):
         if got < 0:
             self._check(int(got))
         return t[:got]
+
+
+def gan_iteration_plan(start_iter: int, train_iters: int, critic_iters: int):
+    """The bookkeeping of ``train_gan``: per iteration (it, k0, generator_step) -- the iteration's index in the whole run, the running
+    index of its first critic step, and whether it starts with a generator step (every iteration but the run's first, gan.py:279)."""
+    return [(it, it * int(critic_iters), it > 0) for it in range(int(start_iter), int(start_iter) + int(train_iters))]
+
+
+def generator_state_arrays(m: Dict[str, np.ndarray], v: Dict[str, np.ndarray], t: int) -> Dict[str, np.ndarray]:
+    """The optimiser's entries of save_generator's .npz: adam_m/<name>, adam_v/<name>, adam_t."""
+    out = {}
+    for name in m:
+        out["adam_m/" + name], out["adam_v/" + name] = m[name], v[name]
+    out["adam_t"] = np.asarray(int(t), np.int64)
+    return out
+
+
+def split_generator_state(arrays: Dict[str, np.ndarray], names):
+    """(m, v, t) from the arrays of a save_generator .npz, or None when it holds the parameters alone."""
+    if "adam_t" not in arrays:
+        return None
+    missing = [p + n for n in names for p in ("adam_m/", "adam_v/") if p + n not in arrays]
+    if missing:
+        raise ValueError("optimiser state lacks %s" % ", ".join(missing))
+    return ({n: np.asarray(arrays["adam_m/" + n], np.float32) for n in names},
+            {n: np.asarray(arrays["adam_v/" + n], np.float32) for n in names}, int(arrays["adam_t"]))
 
 
 def tuning_text_id(text: str) -> str:

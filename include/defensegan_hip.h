@@ -471,6 +471,33 @@ int dg_critic_step(dg_clf* h, const float* real, const float* fake, const float*
                    int penalty_axes, float learning_rate, float beta_a, float beta_b, float* cost, void* stream);
 
 /*
+ * The generator's training step (the generator half of models/gan.py:167-199, 273-293; defensegan_amd/csrc/dg_gen_train.hip's header
+ * comment and DESIGN.md section 7, "The generator step").  Implemented for the MNIST / F-MNIST generator without Batchnorm; a CelebA
+ * or use_bn handle is DG_E_INVALID with "not implemented for ..." in dg_last_error().  z [N, latent]; dy [N,28,28,1] = the gradient
+ * of the loss with respect to the generator's OUTPUT (after the sigmoid) -- for WGAN-GP dg_clf_backward on the critic at x = G(z)
+ * with dlogits = -1/N.  Null pointers, N < 1, N above 2^20 (dg_generate's limit), incomplete weights and unknown names are returned
+ * as errors.  Device pointers; asynchronous on `stream`; the first call of a row count sizes workspaces and job lists (blocking, as
+ * dg_prepare), later calls of it allocate nothing and wait for nothing.  No float atomics: a call repeated returns the same bits.
+ */
+/* Forward on z, then the seeded backward.  grads = the flat gradient in the order and layouts of the parameters -- Generator.Input.W
+ * [latent, 4*4*4*nd], .b, then <layer>.Filters [5,5,Cout,Cin] and .Biases for Generator.2, .3, .5.  out_y [N,28,28,1] = G(z) and
+ * out_dz [N, latent] may be NULL.  Stateless; the weights do not change. */
+int dg_gen_param_gradient(dg_handle* h, const float* z, const float* dy, int N, float* grads, float* out_y, float* out_dz, void* stream);
+/* The same gradient, then one step of tf.train.AdamOptimizer(lr, beta1, beta2, epsilon = 1e-8) in dg_critic_step's form on every
+ * parameter, then the refresh of every derived weight layout of the handle (options frag_path and turn_fused included) on the device:
+ * whatever runs next on the stream -- dg_generate, dg_reconstruct -- sees the new weights.  The moments and the step count are the
+ * handle's own; a later dg_set_weights replaces the parameter and leaves them alone. */
+int dg_gen_step(dg_handle* h, const float* z, const float* dy, int N, float lr, float beta1, float beta2, void* stream);
+/* The current value of a parameter by its reference name (the layout dg_set_weights takes).  Synchronous. */
+int dg_get_weights(dg_handle* h, const char* name, float* out, int is_device);
+/* A fresh optimiser: m = v = 0, t = 0.  Synchronous. */
+int dg_gen_adam_reset(dg_handle* h);
+/* A parameter's Adam moments (its own shape) and the handle's step count t (host); any of m, v, t may be NULL.  Synchronous. */
+int dg_gen_get_adam(dg_handle* h, const char* name, float* m, float* v, int64_t* t, int is_device);
+/* Installs a parameter's moments and sets the handle's step count to t.  Synchronous. */
+int dg_gen_set_adam(dg_handle* h, const char* name, const float* m, const float* v, int64_t t, int is_device);
+
+/*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
  * (no collective on the data path) and ONE all_gather assembles the evaluation message -- per rank `count` int32 words, e.g.
  * [n | labels (cap) | preds (cap) | diffs (cap, float32 bits)] as defensegan_amd/gan_defense.py:model_eval_gan_sharded builds it
