@@ -9,6 +9,8 @@ generator (and every LeakyReLU gate of the critic, when one is given) and no pre
 1e-6 of zero.  At most MAX_SEEDS seeds are tried, starting from the given first seed; the GPU tests hold the found seed as a constant
 and assert it is the first accepted draw.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -53,17 +55,19 @@ def preacts(params, z, dtype=torch.float64):
     return [o.double().numpy() for o in out]
 
 
-def gradient(params, z, dy=None, critic=None, want_acts=False):
+def gradient(params, z, dy=None, critic=None, want_acts=False, dtype=torch.float64):
     """float64: {y, grads {name: array}, dz, cost} for the loss sum(dy * G(z)) (an explicit seed) or -mean D(G(z))
-    (``critic`` = (layers, params) of tests/support/critic_reference.py)."""
-    g = _gen(params, torch.float64)
+    (``critic`` = (layers, params) of tests/support/critic_reference.py).  ``dtype`` = torch.float32 gives the CPU's float32 autograd
+    of the same graph (explicit seed only): what float32 itself costs against the reference."""
+    assert dtype == torch.float64 or critic is None
+    g = _gen(params, dtype)
     leaves = [g.W.requires_grad_(True), g.b.requires_grad_(True)]
     for (w, b, *_rest) in g.layers:
         leaves += [w.requires_grad_(True), b.requires_grad_(True)]
-    zt = torch.as_tensor(np.asarray(z, np.float64)).clone().requires_grad_(True)
+    zt = torch.as_tensor(np.asarray(z, np.float64)).to(dtype).clone().requires_grad_(True)
     y = g.forward(zt)
     if critic is None:
-        loss = (torch.as_tensor(np.asarray(dy, np.float64)).reshape(y.shape) * y).sum()
+        loss = (torch.as_tensor(np.asarray(dy, np.float64)).to(dtype).reshape(y.shape) * y).sum()
     else:
         layers, cparams = critic
         loss = -CR.forward(layers, CR.as_params(cparams), y).mean()
@@ -171,6 +175,67 @@ def find_seed(params, N, latent, first=0, critic=None):
         if accepted(params, z, critic):
             return seed
     raise AssertionError("no accepted seed among %d" % MAX_SEEDS)
+
+
+# (latent, net_dim, N) of the large-batch GPU tests (tests/test_gpu_gen_train_regimes.py), each the smallest N that enters the split
+# regime it is named for; tests/test_gen_train_regimes_cpu.py shows that draw_rows serves every one
+ROW_CASES = [(128, 64, 84), (128, 64, 85), (128, 64, 257), (64, 64, 257), (128, 128, 33)]
+ROW_POOL_CAP = 16           # draw_rows looks at no more than this many times N rows
+ROW_MARGIN_FACTOR = 4.0     # ... and keeps a row whose pre-activations lie this many float32 errors away from zero
+
+
+def draw_rows(latent, nd, N, seed=0, params=None):
+    """(z [N, latent], dy [N,28,28,1], info): the first N rows of draw(seed, pool, latent) none of whose ReLU gates float32 can flip.
+    A whole large batch is never accepted by ``accepted`` (its number of gates grows with N and 2-3 % of the rows have a pre-activation
+    within 1e-6 of zero), but the generator has no Batchnorm, so a row's gates depend on that row alone and rows can be selected.  The selection is computed once per process; every call returns copies of it.
+
+    The pool grows by N rows at a time (draw(seed, pool, latent): z is the head of one stream, so the rows already looked at stay)
+    up to ROW_POOL_CAP * N.  The gate margin is not a constant: per ReLU layer (Linear, Generator.2, Generator.3) it is
+    ROW_MARGIN_FACTOR times the largest |float32 - float64| pre-activation difference over the pool (``preacts`` at both dtypes, one
+    block of N rows at a time).  A row is kept when at EVERY layer all its float64 pre-activations lie farther from zero than that
+    layer's margin.  The factor 4 leaves room for the device's different summation order; the device's own pre-activation error has
+    NOT been measured -- a device whose error exceeded 4 x the CPU's float32 error would show as a gradient failure of the order 1/N of
+    a bias's scale, not as a slightly exceeded bound.
+
+    The float32 forward is the CPU's: another CPU's BLAS gives slightly other differences, so margins, pool and rows may differ from
+    machine to machine (NET_DIM 128, N = 33: 165 rows looked at and 0.23 kept on one, 99 and 0.37 on another); within a process they
+    are fixed.
+
+    ``info``: pool (rows looked at), kept (share of the pool that passed), margins (the three, in layer order).  Raises when
+    ROW_POOL_CAP * N rows do not yield N; asserts that ``accepted`` holds on the returned batch as well.  ``params``: select for
+    these weights (a trained handle's get_weights()) instead of weights(latent, nd); not cached."""
+    if params is not None:
+        return _select_rows(params, latent, N, seed)
+    z, dy, info = _draw_rows(latent, nd, N, seed)
+    return z.copy(), dy.copy(), dict(info)
+
+
+@functools.lru_cache(maxsize=None)
+def _draw_rows(latent, nd, N, seed):
+    return _select_rows(weights(latent, nd), latent, N, seed)
+
+
+def _select_rows(p, latent, N, seed):
+    p64, diff, seen = [], np.zeros(3), np.zeros((0, latent), np.float32)
+    for blocks in range(1, ROW_POOL_CAP + 1):
+        pool = blocks * N
+        z, dy = draw(seed, pool, latent)
+        assert np.array_equal(z[:pool - N], seen)                  # the pool grows at its end
+        seen, zb = z, z[pool - N:]
+        a64, a32 = preacts(p, zb, torch.float64), preacts(p, zb, torch.float32)
+        p64.append([a.reshape(N, -1) for a in a64])
+        diff = np.maximum(diff, [float(np.abs(a - b).max()) for a, b in zip(a64, a32)])
+        margins = ROW_MARGIN_FACTOR * diff
+        keep = np.ones(pool, bool)
+        for layer in range(3):
+            nearest = np.concatenate([np.abs(blk[layer]).min(axis=1) for blk in p64])
+            keep &= nearest > margins[layer]
+        if int(keep.sum()) >= N:
+            rows = np.flatnonzero(keep)[:N]
+            info = {"pool": pool, "kept": float(keep.mean()), "margins": [float(m) for m in margins]}
+            assert accepted(p, z[rows]), "the selected rows are not an accepted batch"
+            return np.ascontiguousarray(z[rows]), np.ascontiguousarray(dy[rows]), info
+    raise AssertionError("%d rows of seed %d do not yield %d with every gate outside its margin" % (ROW_POOL_CAP * N, seed, N))
 
 
 def adam_f32(p, g, m, v, t, lr, b1, b2):
