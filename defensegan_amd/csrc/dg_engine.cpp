@@ -1018,6 +1018,7 @@ int dg_destroy(dg_handle* h) {
     (void)hipSetDevice(h->device);
     prof_collect(h);
     gen_train_release(h);
+    latent_release(h);
     if (h->turn_err_host) { (void)hipHostFree(h->turn_err_host); h->turn_err_host = nullptr; }
     drop_graphs(h);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);

@@ -147,6 +147,7 @@ struct dg_handle {
     // through that packer's gather map.  pack_epoch counts the (re)allocations of derived buffers: maps of an older epoch are rebuilt.
     uint64_t pack_epoch = 0;
     struct GenTrain* gen_train = nullptr;   // workspace, Adam state and gather maps of the training step (dg_gen_train.hip), or nullptr
+    struct LatentWork* latent_work = nullptr;   // workspace of the latent-space attack (dg_latent.hip), or nullptr
     std::vector<float*> F, Ft, bias;   // per deconv: [25][cout][cin], [25][cin][cout], [cout]
     std::vector<float*> Fp;            // per non-final deconv: the forward filters in fragment order (dg_fgemm.hip), per tap slab
                                        // [cout / 32][cin / 8][64][4]
@@ -360,6 +361,9 @@ bool lin_pack_fwd_shapes(const dg_handle* h);
 bool lin_pack_bwd_shapes(const dg_handle* h);
 // ---- dg_gen_train.hip
 void gen_train_release(dg_handle* h);
+// ---- dg_latent.hip
+void latent_release(dg_handle* h);
+// ---- dg_engine.cpp
 bool lin_stationary(const dg_handle* h, const GemmOp& op);
 bool frag_on(const dg_handle* h);
 int build_lin_packs(dg_handle* h);

@@ -35,6 +35,7 @@
 // (lin_wt, the Linear packs, Ft, Fp, the tail packs) are refreshed by gather maps made once per handle by running the packers of
 // dg_pack.h on an index array: dst[i] = map[i] < 0 ? 0 : src[map[i]].  Neither a host round trip nor a synchronisation.
 #include "dg_engine.h"
+#include "dg_gen_internal.h"
 #include "dg_pack.h"
 
 struct GenTrain {
@@ -258,13 +259,6 @@ long long param_total(const dg_handle* h) {
     return v.back().off + v.back().n;
 }
 
-// what the training entry points refuse, by name
-int check_trainable(const dg_handle* h, const char* who) {
-    if (h->arch != DG_ARCH_MNIST28) return fail(DG_E_INVALID, "%s: not implemented for the CelebA generator (only the MNIST / F-MNIST one)", who);
-    if (h->use_bn) return fail(DG_E_INVALID, "%s: not implemented for use_bn (a Batchnorm generator)", who);
-    return DG_OK;
-}
-
 struct SplitPlan { int chunks; long long len; };
 // a reduction axis of `total` terms in at most `max_chunks` chunks of at least `min_len`: a function of the shapes alone
 SplitPlan split_axis(long long total, int max_chunks, long long min_len, long long multiple) {
@@ -395,26 +389,6 @@ int build_maps(dg_handle* h, GenTrain* g) {
     return DG_OK;
 }
 
-// The training forward and backward read and write the NHWC activation buffers: a handle on the fragment-order path (option
-// frag_path) runs these calls on the NHWC path, with the job lists of that path, and returns to its own afterwards.
-// This is NOT dg_set_option("frag_path"): the option frees the workspace and drops the job lists because the handle changes path
-// for good; here both paths must stay usable side by side, so nothing is freed and the flag only selects, for the length of one call,
-// which launches run_forward / run_backward make and which kind of list prepare_rows looks for.  Two consequences the caller of
-// this scope (gen_call) relies on and must keep:
-//   * prepare_rows runs once BEFORE the scope, with the handle's own path.  Only that call may grow the workspace: grown inside
-//     the scope it would come back without the fragment-order buffers (ensure_workspace sizes them by frag_path), and the
-//     handle's next projection call would quietly leave its path.  Inside the scope the workspace is already large enough and
-//     the second prepare_rows only adds the NHWC forward lists the fragment-order path never built.
-//   * the backward layers' lists are shared by both paths.  On a frag_path handle they were TIMED with the gate-bit epilogue and
-//     run here with the in-place mask: the choice among equally correct, bit-identical lists may then not be the fastest for
-//     this epilogue.  Results do not depend on it (tests/test_gpu_gen_train.py, the frag_path case of the refresh test).
-struct NhwcScope {
-    dg_handle* h;
-    int saved;
-    explicit NhwcScope(dg_handle* h_) : h(h_), saved(h_->frag_path) { h->frag_path = 0; }
-    ~NhwcScope() { h->frag_path = saved; }
-};
-
 int launch_wgrad(dg_handle* h, GenTrain* g, const WgradShape& w, const float* A, const float* B, int N, float* out, hipStream_t s, bool prof,
                  const char* name) {
     const SplitPlan sp = wgrad_split(w, N);
@@ -505,7 +479,7 @@ int gen_call(dg_handle* h, const float* z, const float* dy, int N, float* grads,
              float b2, void* stream, const char* who) {
     if (!h) return fail(DG_E_INVALID, "%s: null handle", who);
     if (!z || !dy || (!adam && !grads)) return fail(DG_E_INVALID, "%s: null argument", who);
-    int rc = check_trainable(h, who);
+    int rc = gen_check_trainable(h, who);
     if (rc) return rc;
     if ((rc = check_ready(h))) return rc;
     int n_checked = 0;
@@ -554,6 +528,20 @@ const ParamSeg* find_seg(const std::vector<ParamSeg>& segs, const char* name) {
 
 #pragma GCC visibility push(hidden)
 namespace dge {
+int gen_check_trainable(const dg_handle* h, const char* who) {
+    if (h->arch != DG_ARCH_MNIST28) return fail(DG_E_INVALID, "%s: not implemented for the CelebA generator (only the MNIST / F-MNIST one)", who);
+    if (h->use_bn) return fail(DG_E_INVALID, "%s: not implemented for use_bn (a Batchnorm generator)", who);
+    return DG_OK;
+}
+
+void gen_launch_seed(const float* dy, const float* y, float* dpre5, long long n, hipStream_t s) {
+    hipLaunchKernelGGL(gen_seed_kernel, dim3(grid_of(n)), dim3(256), 0, s, dy, y, dpre5, n);
+}
+
+void gen_launch_tail_bwd(float* h3, const float* dpre5, const float* F5, long long total, int C, hipStream_t s) {
+    hipLaunchKernelGGL(gen_tail_bwd_kernel, dim3(grid_of(total)), dim3(256), 0, s, h3, dpre5, F5, total, C);
+}
+
 void gen_train_release(dg_handle* h) {
     GenTrain* g = h->gen_train;
     if (!g) return;
@@ -592,7 +580,7 @@ int dg_get_weights(dg_handle* h, const char* name, float* out, int is_device) {
 
 int dg_gen_adam_reset(dg_handle* h) {
     if (!h) return fail(DG_E_INVALID, "dg_gen_adam_reset: null handle");
-    int rc = check_trainable(h, "dg_gen_adam_reset");
+    int rc = gen_check_trainable(h, "dg_gen_adam_reset");
     if (rc) return rc;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -607,7 +595,7 @@ int dg_gen_adam_reset(dg_handle* h) {
 
 int dg_gen_get_adam(dg_handle* h, const char* name, float* m, float* v, int64_t* t, int is_device) {
     if (!h || !name) return fail(DG_E_INVALID, "dg_gen_get_adam: null argument");
-    int rc = check_trainable(h, "dg_gen_get_adam");
+    int rc = gen_check_trainable(h, "dg_gen_get_adam");
     if (rc) return rc;
     const auto segs = param_segs(h);
     const ParamSeg* p = find_seg(segs, name);
@@ -629,7 +617,7 @@ int dg_gen_get_adam(dg_handle* h, const char* name, float* m, float* v, int64_t*
 
 int dg_gen_set_adam(dg_handle* h, const char* name, const float* m, const float* v, int64_t t, int is_device) {
     if (!h || !name || !m || !v || t < 0) return fail(DG_E_INVALID, "dg_gen_set_adam: bad argument");
-    int rc = check_trainable(h, "dg_gen_set_adam");
+    int rc = gen_check_trainable(h, "dg_gen_set_adam");
     if (rc) return rc;
     const auto segs = param_segs(h);
     const ParamSeg* p = find_seg(segs, name);

@@ -1030,3 +1030,130 @@ def rand_fgsm_prestep(test_images, eps: float, alpha: float, min_val: float = 0.
     x = np.asarray(test_images, np.float32)
     out = np.clip(x + np.float32(alpha) * np.sign(rng.randn(*x.shape)).astype(np.float32), min_val, max_val).astype(np.float32)
     return out, float(eps) - float(alpha)
+
+
+LATENT_DEFAULT_SEED = 11241990
+
+
+class LatentAttack(object):
+    """The latent-space attack (Athalye, Carlini, Wagner 2018, section 5), the attack that breaks Defense-GAN: search the generator's
+    range for ``z`` such that ``G(z)`` is misclassified and close to ``x``.  ``G(z)`` lies on the manifold, so the projection returns
+    it almost unchanged and the defence does not help.  One asynchronous device call per ``batch_size`` images (``dg_latent_attack``,
+    defensegan_amd/csrc/dg_latent.hip; DESIGN.md section 7 gives the definition): ``rec_rr`` restarts per image, TF's Adam
+    (0.9, 0.999, 1e-8) on ``z`` for ``nb_iter`` steps of the loss
+
+        mean_pixels (G(z) - x)^2 + c max(logits[y] - max_{k != y} logits[k] + confidence, 0)
+
+    and per image the successful iterate (margin < -confidence) of the smallest distance, or -- with no success -- the final iterate
+    of the smallest margin.
+
+    ``model``: an MLP whose output before Softmax is the logits, without Dropout.  A model with the reconstruction layer attached
+    (``add_rec_model``) is accepted: the attack uses its BARE classifier and, when ``gan`` is None, the layer's generator.  ``gan``:
+    a DefenseGANBase of the MNIST / F-MNIST architecture with ``USE_BN: False``; a CelebA or Batchnorm generator raises
+    NotImplementedError with the library's words.
+
+    ``generate`` returns ``x_adv`` (NumPy in, NumPy out; a device tensor in, a device tensor out on the caller's current stream, not
+    waited for); ``return_info=True`` adds a dict of best_dist, best_margin [n], best_iter, best_row [n] int32 (best_iter = -1: no
+    success) and z [n rec_rr, latent].  ``y``: class indices or one-hot rows, required, checked on the host against the class count.
+    ``z_init`` [n rec_rr, latent] or None: the rows are then drawn as ``init_latents(seed)`` draws them, keyed by the GLOBAL row
+    (image index x rec_rr + restart), so the result does not depend on ``batch_size``, which only bounds the images per call."""
+
+    def __init__(self, model: MLP, gan=None, back="tf", sess=None):
+        self.model = model
+        if gan is None and model.rec_layer is not None:
+            gan = model.rec_layer.rec_model
+        if gan is None:
+            raise ValueError("LatentAttack needs the generator: pass gan, or a model with the reconstruction layer attached")
+        self.gan = gan
+
+    def _check_gan(self):
+        from . import archs
+        g = self.gan
+        if g._arch.arch_id == archs.ARCH_CELEBA:
+            raise NotImplementedError("dg_latent_attack: not implemented for the CelebA generator (only the MNIST / F-MNIST one)")
+        if g.use_bn:
+            raise NotImplementedError("dg_latent_attack: not implemented for use_bn (a Batchnorm generator)")
+
+    def call(self, x, labels, R, nb_iter, learning_rate=0.05, c=1.0, confidence=0.0, z0=None, seed=0, first_row=0, beta1=0.9, beta2=0.999,
+             m=None, v=None, t_start=0, keep_state=False, state=None, traces=False, want_dz=False):
+        """One ``dg_latent_attack`` call on device tensors: ``x`` [B,28,28,1] float32, ``labels`` [B] int32.  ``state``: the dict a
+        call before returned, whose x_adv / best_* buffers this call continues (``t_start`` > 0).  Returns a dict of device tensors:
+        x_adv, best_dist, best_margin, best_iter, best_row, z, and with ``traces`` margin and dist [nb_iter + 1, B R], with
+        ``want_dz`` dz [B R, latent].  Nothing is waited for."""
+        import torch
+        g, mdl = self.gan, self.model
+        self._check_gan()
+        g._ensure_handle()
+        if not g.initialized:
+            raise _native.NativeError("generator weights not loaded (load_generator / set_weights)")
+        mdl._ensure()
+        dev = x.device
+        B, N, latent = int(x.shape[0]), int(x.shape[0]) * int(R), int(g.latent_dim)
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        out = dict(state) if state is not None else {
+            "x_adv": torch.empty_like(x), "best_dist": f32(B), "best_margin": f32(B),
+            "best_iter": torch.empty(B, dtype=torch.int32, device=dev), "best_row": torch.empty(B, dtype=torch.int32, device=dev)}
+        out["z"] = f32(N, latent)
+        if traces:
+            out["margin"], out["dist"] = f32(int(nb_iter) + 1, N), f32(int(nb_iter) + 1, N)
+        if want_dz:
+            out["dz"] = f32(N, latent)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(dev):
+            _native.check(g._lib().dg_latent_attack(
+                g._handle, mdl._handle, x.data_ptr(), labels.data_ptr(), B, int(R), ptr(z0), int(seed), int(first_row), int(nb_iter),
+                float(learning_rate), float(beta1), float(beta2), float(c), float(confidence), ptr(m), ptr(v), int(t_start),
+                1 if keep_state else 0, out["x_adv"].data_ptr(), out["best_dist"].data_ptr(), out["best_margin"].data_ptr(),
+                out["best_iter"].data_ptr(), out["best_row"].data_ptr(), out["z"].data_ptr(), ptr(out.get("margin")), ptr(out.get("dist")),
+                ptr(out.get("dz")), torch.cuda.current_stream(dev).cuda_stream), g._lib())
+        return out
+
+    def generate(self, x, y, rec_rr=None, nb_iter=100, learning_rate=0.05, c=1.0, confidence=0.0, z_init=None, seed=None, batch_size=None,
+                 return_info=False):
+        import torch
+        self._check_gan()
+        mdl, g = self.model, self.gan
+        R = int(g.rec_rr if rec_rr is None else rec_rr)
+        nb_iter = int(nb_iter)
+        if R < 1 or nb_iter < 0:
+            raise ValueError("rec_rr must be >= 1 and nb_iter >= 0")
+        if not (float(confidence) >= 0 and float(c) >= 0):
+            raise ValueError("confidence and c must be >= 0")
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        seed = LATENT_DEFAULT_SEED if seed is None else int(seed)
+        mdl._ensure()
+        if not mdl._weights_set:
+            raise _native.NativeError("classifier weights not set")
+        g._ensure_handle()
+        dev = torch.device("cuda", mdl._device)
+        was_numpy = isinstance(x, np.ndarray)
+        to = lambda a: (torch.from_numpy(np.ascontiguousarray(a, np.float32)) if isinstance(a, np.ndarray) else a).to(device=dev, dtype=torch.float32).contiguous()
+        t = to(x)
+        if t.dim() != 4 or tuple(t.shape[1:]) != tuple(mdl.input_shape[1:]) or int(t.shape[0]) == 0:
+            raise ValueError("x must be [n, %s] with n > 0, got %s" % (", ".join(str(d) for d in mdl.input_shape[1:]), tuple(t.shape)))
+        n = int(t.shape[0])
+        yy = np.asarray(y if isinstance(y, np.ndarray) else (y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y))
+        if yy.ndim > 1:
+            yy = yy.argmax(axis=-1)
+        if yy.shape != (n,):
+            raise ValueError("y must be %d class indices or one-hot rows" % n)
+        if (yy < 0).any() or (yy >= mdl.nb_classes).any():
+            raise ValueError("y holds a class index outside [0, %d)" % mdl.nb_classes)
+        lab = torch.from_numpy(np.ascontiguousarray(yy.astype(np.int32))).to(dev)
+        z0 = None
+        if z_init is not None:
+            z0 = to(z_init)
+            if tuple(z0.shape) != (n * R, int(g.latent_dim)):
+                raise ValueError("z_init must be [%d, %d], got %s" % (n * R, int(g.latent_dim), tuple(z0.shape)))
+        bs = n if batch_size is None else int(batch_size)
+        parts = []
+        for a in range(0, n, bs):
+            b = min(n, a + bs)
+            parts.append(self.call(t[a:b], lab[a:b], R, nb_iter, learning_rate, c, confidence, None if z0 is None else z0[a * R:b * R],
+                                   seed, a * R))
+        info = {k: torch.cat([p[k] for p in parts]) for k in ("x_adv", "best_dist", "best_margin", "best_iter", "best_row", "z")}
+        x_adv = info.pop("x_adv")
+        if was_numpy:
+            x_adv, info = x_adv.cpu().numpy(), {k: v.cpu().numpy() for k, v in info.items()}
+        return (x_adv, info) if return_info else x_adv

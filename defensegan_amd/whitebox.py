@@ -2,14 +2,16 @@
 device:
 
     whitebox    trains the classifier (cleverhans model_train; ``adv_tr`` adds FGSM inputs; ``train_on_recs`` trains on cached
-                reconstructions), attacks the ORIGINAL test images (fgsm, rand_fgsm, cw -- and pgd on a bare model, bpda on a
-                defended one, which the reference has not) and measures the accuracy on the adversarial images, through the
+                reconstructions), attacks the ORIGINAL test images (fgsm, rand_fgsm, cw -- and pgd on a bare model, bpda and latent
+                on a defended one, which the reference has not) and measures the accuracy on the adversarial images, through the
                 Defense-GAN projection for ``defense_gan`` (with the ROC triple)                       whitebox.py:56-233
     main        the flags and the result files of whitebox.py:236-392
 
     python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --defense_type none --attack_type pgd
     python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --init_path output/gans/mnist \\
         --defense_type defense_gan --attack_type bpda --results_dir run0
+    python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --init_path output/gans/mnist \\
+        --defense_type defense_gan --attack_type latent --latent_iters 100 --rec_rr 10
 
 Kept from the reference: ``RandomState([11, 24, 1990])`` for the training schedule; the clean accuracy on the (reconstructed) test
 split printed after every epoch; with ``defense_gan`` the reconstruction layer is attached AFTER training and BEFORE the attack
@@ -25,10 +27,12 @@ import numpy as np
 from . import config, datasets, gan_defense, network_builder, py2pickle, utils_tf
 from .blackbox import SEED, _Phase, _accuracy, _labels, load_recs, result_path
 
-ATTACKS = ("fgsm", "cw", "pgd", "bpda")
+ATTACKS = ("fgsm", "cw", "pgd", "bpda", "latent")
 # whitebox.py:203-209; 'feed' is TensorFlow's business
 CW_PARAMS = {"binary_search_steps": 1, "max_iterations": 100, "learning_rate": 10.0, "initial_const": 100}
 ITERATIVE_DEFAULTS = {"eps_iter": 0.05, "nb_iter": 10, "eot_samples": 1}
+# the latent-space attack (network_builder.LatentAttack): Adam steps on z, their learning rate, the weight of the classification term
+LATENT_DEFAULTS = {"latent_iters": 100, "latent_lr": 0.05, "latent_c": 1.0}
 PGD_CALL_IMAGES = 10000                       # images per dg_pgd call: bounds the kept activations, not the result
 
 
@@ -42,9 +46,9 @@ def attack_kind(attack_type):
     if "fgsm" in t:
         return "fgsm", rand
     base = t.replace("rand", "").strip("_+")
-    if base in ATTACKS and not (rand and base == "cw"):
+    if base in ATTACKS and not (rand and base in ("cw", "latent")):
         return base, rand
-    raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, pgd (defense_type none / adv_tr) or bpda (defense_gan)" % (attack_type,))
+    raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, pgd (defense_type none / adv_tr), bpda or latent (defense_gan)" % (attack_type,))
 
 
 def attack_ord_value(attack_ord, kind=None):
@@ -52,19 +56,21 @@ def attack_ord_value(attack_ord, kind=None):
     takes 1 and 2 (``FastGradientMethod``'s ord), pgd and bpda take 2 (1 is NotImplementedError: the L1 projection needs a sort), cw
     is an L2 attack already and takes none."""
     who = "attack_ord" if kind is None else "attack_ord with attack_type %s" % kind
-    allowed = {"fgsm": (np.inf, 1, 2), "pgd": (np.inf, 2), "bpda": (np.inf, 2), "cw": (np.inf,)}.get(kind, (np.inf, 1, 2))
+    allowed = {"fgsm": (np.inf, 1, 2), "pgd": (np.inf, 2), "bpda": (np.inf, 2), "cw": (np.inf,), "latent": (np.inf,)}.get(kind, (np.inf, 1, 2))
     return network_builder._attack_ord(attack_ord, allowed, who)
 
 
 def _attack_params(kind, attack_params):
     """The overrides ``attack_params`` holds for this attack: eps_iter / nb_iter (pgd, bpda), eot_samples (bpda), any
-    CarliniWagnerL2 parameter (cw).  Values of None and the iterative attacks' keys given to another attack are left out."""
+    CarliniWagnerL2 parameter (cw), latent_iters / latent_lr / latent_c (latent).  Values of None and the iterative attacks' keys given to another attack are left out."""
     given = {k: v for k, v in (attack_params or {}).items() if v is not None}
-    known = set(ITERATIVE_DEFAULTS) | set(network_builder.CarliniWagnerL2.DEFAULTS)
+    known = set(ITERATIVE_DEFAULTS) | set(network_builder.CarliniWagnerL2.DEFAULTS) | set(LATENT_DEFAULTS)
     if set(given) - known:
         raise ValueError("unknown attack_params: %s" % sorted(set(given) - known))
     if kind == "cw":
         return {k: v for k, v in given.items() if k in network_builder.CarliniWagnerL2.DEFAULTS}
+    if kind == "latent":
+        return {k: given.get(k, d) for k, d in LATENT_DEFAULTS.items()}
     keys = {"pgd": ("eps_iter", "nb_iter"), "bpda": ("eps_iter", "nb_iter", "eot_samples")}.get(kind, ())
     return {k: given.get(k, ITERATIVE_DEFAULTS[k]) for k in keys}
 
@@ -90,6 +96,8 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
       cw                CarliniWagnerL2 with binary_search_steps 1, max_iterations 100, learning_rate 10, initial_const 100
       pgd               ProjectedGradientDescent on the true labels: 'none' and 'adv_tr' only
       bpda              BPDA on the true labels: 'defense_gan' only
+      latent            LatentAttack on the true labels, ``gan.rec_rr`` restarts per image: 'defense_gan' only.  x_adv = G(z) lies in
+                        the generator's range, not in the ``eps`` ball; ``attack_params`` latent_iters (100), latent_lr (0.05), latent_c (1)
     ``attack_params`` overrides ``eps_iter`` (0.05), ``nb_iter`` (10), ``eot_samples`` (1) of pgd / bpda and any CarliniWagnerL2
     parameter.  pgd with 'defense_gan' or bpda without it is a ValueError.  ``attack_ord`` (default np.inf): 2 runs pgd / bpda in an
     L2 ball of radius ``eps`` (their ``ord``), 1 or 2 runs fgsm / rand_fgsm as FGM with that norm; 1 with pgd / bpda is
@@ -120,6 +128,9 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
         if kind[0] == "bpda" and not defended:
             raise ValueError("attack_type bpda needs the projection (defense_type defense_gan); on a bare classifier (%s) the "
                              "iterative attack is pgd" % defense_type)
+        if kind[0] == "latent" and not defended:
+            raise ValueError("attack_type latent searches the generator's range and needs the projection (defense_type defense_gan), "
+                             "not %s" % defense_type)
         if kind[0] == "bpda" and same_init:
             raise ValueError("attack_type bpda draws fresh latents for every projection: not with same_init")
         extra = _attack_params(kind[0], attack_params)
@@ -193,6 +204,10 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
             attack = network_builder.ProjectedGradientDescent(model)
             x_adv = attack.generate(test_adv_from, test_labels, eps=eps, clip_min=min_val, clip_max=1.0, seed=seed,
                                     batch_size=PGD_CALL_IMAGES, **extra)
+        elif kind == "latent":
+            attack = network_builder.LatentAttack(model, gan)
+            x_adv = attack.generate(test_adv_from, test_labels, rec_rr=int(gan.rec_rr), nb_iter=int(extra["latent_iters"]),
+                                    learning_rate=float(extra["latent_lr"]), c=float(extra["latent_c"]), seed=seed, batch_size=batch_size)
         else:
             attack = network_builder.BPDA(model)
             x_adv = attack.generate(test_adv_from, test_labels, eps=eps, clip_min=min_val, clip_max=1.0, seed=seed, batch_size=batch_size,
@@ -269,7 +284,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--random_test_iter", type=int, default=-1, help="accepted and ignored, as in the reference")
     ap.add_argument("--online_training", action="store_true", help="not implemented (NotImplementedError)")
     ap.add_argument("--defense_type", default="none", choices=["none", "defense_gan", "adv_tr"], help="Type of defense")
-    ap.add_argument("--attack_type", default="none", help="Type of attack [fgsm|cw|rand_fgsm|pgd|bpda]; none: train and stop")
+    ap.add_argument("--attack_type", default="none", help="Type of attack [fgsm|cw|rand_fgsm|pgd|bpda|latent]; none: train and stop")
     ap.add_argument("--results_dir", default=None, help="The final subdirectory of the results.")
     ap.add_argument("--model", default="F", choices=sorted(network_builder.MODELS), help="The classifier model.")
     ap.add_argument("--debug_dir", default="temp", help="accepted and ignored (the reference's qualitative debug output)")
@@ -279,6 +294,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eps_iter", type=float, default=None, help="pgd / bpda step size (default 0.05)")
     ap.add_argument("--nb_iter", type=int, default=None, help="pgd / bpda iterations (default 10)")
     ap.add_argument("--eot_samples", type=int, default=None, help="bpda: projections the gradient is summed over per iteration (default 1)")
+    ap.add_argument("--latent_iters", type=int, default=None, help="latent: Adam steps on z (default 100); --rec_rr is its restarts per image")
+    ap.add_argument("--latent_lr", type=float, default=None, help="latent: Adam's learning rate (default 0.05)")
+    ap.add_argument("--latent_c", type=float, default=None, help="latent: weight of the classification term (default 1)")
     ap.add_argument("--attack_ord", default="inf", choices=["inf", "1", "2"],
                     help="norm of the attack's ball: pgd / bpda take inf or 2, fgsm / rand_fgsm inf, 1 or 2 (default inf)")
     ap.add_argument("--seed", type=int, default=SEED, help="seed of the Dropout masks and the latent draws")
@@ -326,7 +344,8 @@ def main(argv=None) -> int:
                           online_training=args.online_training, train_on_recs=args.train_on_recs, attack_type=args.attack_type,
                           defense_type=args.defense_type, num_tests=args.num_tests, num_train=args.num_train,
                           fgsm_eps_tr=args.fgsm_eps_tr, same_init=args.same_init, recs=recs,
-                          attack_params={"eps_iter": args.eps_iter, "nb_iter": args.nb_iter, "eot_samples": args.eot_samples},
+                          attack_params={"eps_iter": args.eps_iter, "nb_iter": args.nb_iter, "eot_samples": args.eot_samples,
+                                         "latent_iters": args.latent_iters, "latent_lr": args.latent_lr, "latent_c": args.latent_c},
                           seed=args.seed, init_seed=args.init_seed, attack_ord=args.attack_ord)
     write_results(path, accuracies)
     return 0

@@ -498,6 +498,46 @@ int dg_gen_get_adam(dg_handle* h, const char* name, float* m, float* v, int64_t*
 int dg_gen_set_adam(dg_handle* h, const char* name, const float* m, const float* v, int64_t t, int is_device);
 
 /*
+ * The latent-space attack (no reference counterpart; Athalye, Carlini, Wagner 2018, section 5; defensegan_amd/csrc/dg_latent.hip's
+ * header comment and DESIGN.md section 7, "The latent-space attack"): TF's Adam on z so that G(z) is misclassified by the bare
+ * classifier `c` and close to x.  `g` is a generator of the MNIST / F-MNIST architecture without Batchnorm (a CelebA or use_bn handle
+ * is DG_E_INVALID with "not implemented for ..." in dg_last_error()); `c` a classifier of [28,28,1] inputs with at least two classes
+ * and no Dropout layer before its logits, on the same device.  x [B,28,28,1] in generator range, labels [B] int32; R restarts per
+ * image, row j = i R + r belongs to image i.  z0 [B*R, latent], or NULL: the rows are drawn as dg_init_latents(seed, first_row) draws
+ * them (std sqrt(1/latent)), keyed by the global row first_row + j.  Per iteration k < nb_iter and row j:
+ *     y = G(z_j);  Z = logits(y);  m_j = Z[label_i] - max_{c != label_i} Z[c] (the first maximum on ties, at o_j);
+ *     d_j = mean over the pixels of (y - x_i)^2;   the loss is d_j + cweight max(m_j + kappa, 0);
+ *     dy = dg_clf_backward's bits for dlogits = (+cweight at label_i, -cweight at o_j) if m_j + kappa > 0 else 0, plus 2 (y - x_i) / 784;
+ *     dz_j = what dg_gen_param_gradient returns as out_dz for this dy;   z_j <- Adam(z_j, dz_j), epsilon 1e-8, dg_critic_step's form,
+ *     lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) in float64 on the host with t = t_start + k + 1.
+ * Unless keep_state != 0, one closing forward (k = nb_iter) judges the last iterate: nb_iter + 1 forwards, nb_iter backwards.
+ * Tracking, per image, over every evaluated row (k, r): a success is m_j < -kappa; the result is the success of the smallest d_j
+ * (ties: the earliest k, then the smallest r) and best_iter = t_start + k; while there is none, the row of the smallest m_j (smallest
+ * r) of the iterate judged last, with best_iter = -1.
+ *   m, v        [B*R, latent] Adam's moments, read and updated in place; both NULL: a fresh optimiser (zero moments, needs t_start 0)
+ *   t_start     Adam steps already taken.  t_start > 0 CONTINUES an attack: the tracker then starts from what x_adv, best_dist,
+ *               best_margin, best_iter, best_row hold (pass the buffers of the call before), so that nb_iter = 3 equals three calls of
+ *               nb_iter = 1 with keep_state (z0 = the out_z before, t_start = 0, 1, 2) followed by one of nb_iter = 0, bit for bit
+ *               (t_start > 0 with m, v or one of the best_* pointers NULL is DG_E_INVALID)
+ *   x_adv       [B,28,28,1] the winning row's G(z), as the forward wrote it (required)
+ *   best_dist, best_margin [B], best_iter, best_row [B] int32 (the r)                           (each may be NULL)
+ *   out_z       [B*R, latent] the final z                                                       (may be NULL)
+ *   out_margin, out_dist [nb_iter + 1, B*R] m_j and d_j of every evaluated iterate of THIS call, row k = its k-th forward; with
+ *               keep_state row nb_iter is not written                                           (may be NULL)
+ *   out_dz      [B*R, latent] dz of the call's last backward; not written when nb_iter = 0      (may be NULL: a test hook)
+ * Labels are device memory and are trusted: one outside [0, classes) reads nothing, gives its rows a zero classification term and
+ * the margin +inf (never a success).  Errors: null pointers, B*R < 1 or above 2^20 (dg_generate's limit), betas outside [0, 1),
+ * kappa < 0, cweight < 0, nb_iter < 0, incomplete weights of either handle (DG_E_STATE).  Device pointers; asynchronous on `stream`;
+ * the first call of a row count sizes workspaces and job lists (blocking, as dg_prepare), later calls of it allocate nothing and
+ * wait for nothing.  No float atomics, every sum in a fixed order: a call repeated returns the same bits, and an image's result does
+ * not depend on which other images share the call.
+ */
+int dg_latent_attack(dg_handle* g, dg_clf* c, const float* x, const int32_t* labels, int B, int R, const float* z0, uint64_t seed,
+                     int64_t first_row, int nb_iter, float lr, float beta1, float beta2, float cweight, float kappa, float* m, float* v,
+                     int64_t t_start, int keep_state, float* x_adv, float* best_dist, float* best_margin, int32_t* best_iter,
+                     int32_t* best_row, float* out_z, float* out_margin, float* out_dist, float* out_dz, void* stream);
+
+/*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
  * (no collective on the data path) and ONE all_gather assembles the evaluation message -- per rank `count` int32 words, e.g.
  * [n | labels (cap) | preds (cap) | diffs (cap, float32 bits)] as defensegan_amd/gan_defense.py:model_eval_gan_sharded builds it
