@@ -20,7 +20,10 @@
 // through latent_track_kernel (one workgroup per image): a row succeeds when m_j < -kappa; the image keeps the successful (k, r) of
 // the smallest d_j (ties: the earliest k, then the smallest r) and, while it has none, the smallest-margin row of the iterate just
 // judged (smallest r on ties) with best_iter = -1 -- which the closing forward leaves as the final iterate's.  The winning row of y
-// is copied into x_adv as the forward wrote it.
+// is copied into x_adv as the forward wrote it.  Non-finite values: a row whose margin is NaN is never a success and never the
+// smallest margin; a successful row whose distance is NaN is never taken; if every margin of the iterate is NaN the no-success
+// result is row 0; +inf compares as a number.  Refused: a call that would evaluate nothing (nb_iter = 0 with keep_state and
+// t_start = 0: x_adv and best_* would stay unwritten), and t_start + nb_iter above INT32_MAX (best_iter is int32).
 //
 // No float atomics, every sum has a fixed order, nothing reads the device between the first and the last launch: two identical
 // calls return identical bits, and an image's result does not depend on which other images share the call.  fp32; gfx950.
@@ -269,6 +272,11 @@ extern "C" int dg_latent_attack(dg_handle* h, dg_clf* c, const float* x, const i
     if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f))
         return fail(DG_E_INVALID, "%s: betas (%g, %g) outside [0, 1)", who, (double)beta1, (double)beta2);
     if (nb_iter < 0 || t_start < 0) return fail(DG_E_INVALID, "%s: need nb_iter >= 0 and t_start >= 0 (got %d, %lld)", who, nb_iter, (long long)t_start);
+    if (nb_iter == 0 && keep_state && t_start == 0)
+        return fail(DG_E_INVALID, "%s: nb_iter = 0 with keep_state and t_start = 0 evaluates nothing: no iterate would be judged and x_adv and best_* would stay unwritten", who);
+    // (the tracker's iterate number and best_iter are int32)
+    if (t_start > (int64_t)INT32_MAX - nb_iter)
+        return fail(DG_E_INVALID, "%s: t_start + nb_iter (%lld + %d) does not fit best_iter (int32)", who, (long long)t_start, nb_iter);
     if (!(kappa >= 0.f) || !(cweight >= 0.f) || !std::isfinite(lr))
         return fail(DG_E_INVALID, "%s: need kappa >= 0, cweight >= 0 and a finite learning rate", who);
     if ((m == nullptr) != (v == nullptr)) return fail(DG_E_INVALID, "%s: give both moments or neither", who);

@@ -527,7 +527,11 @@ int dg_gen_set_adam(dg_handle* h, const char* name, const float* m, const float*
  *   out_dz      [B*R, latent] dz of the call's last backward; not written when nb_iter = 0      (may be NULL: a test hook)
  * Labels are device memory and are trusted: one outside [0, classes) reads nothing, gives its rows a zero classification term and
  * the margin +inf (never a success).  Errors: null pointers, B*R < 1 or above 2^20 (dg_generate's limit), betas outside [0, 1),
- * kappa < 0, cweight < 0, nb_iter < 0, incomplete weights of either handle (DG_E_STATE).  Device pointers; asynchronous on `stream`;
+ * kappa < 0, cweight < 0, nb_iter < 0, nb_iter = 0 with keep_state and t_start = 0 (nothing would be evaluated and the outputs would
+ * stay unwritten; with t_start > 0 it is legal and leaves the passed state and x_adv as they are, out_z = z0), t_start + nb_iter
+ * above INT32_MAX (best_iter is int32), incomplete weights of either handle (DG_E_STATE).  A row whose margin is NaN is never a
+ * success and never the smallest margin, a successful row whose distance is NaN is never taken, all-NaN margins give row 0, +inf
+ * compares as a number.  Device pointers; asynchronous on `stream`;
  * the first call of a row count sizes workspaces and job lists (blocking, as dg_prepare), later calls of it allocate nothing and
  * wait for nothing.  No float atomics, every sum in a fixed order: a call repeated returns the same bits, and an image's result does
  * not depend on which other images share the call.

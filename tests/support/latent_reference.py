@@ -28,6 +28,8 @@ DZ_TOL, SCALAR_TOL = 1e-4, 1e-5
 KINDS = {
     # a three-class classifier of one Linear layer
     "lin3": [("flatten",), ("linear", 3)],
+    # two classes, the fewest the attack accepts: o is the only other class
+    "lin2": [("flatten",), ("linear", 2)],
     # Conv2D / ReLU / Linear, 10 classes: the convolution of generator_reference.fixed_critic (8 channels, 5x5, stride 2, SAME)
     "conv10": [("conv", 8, (5, 5), (2, 2), "SAME"), ("relu",), ("flatten",), ("linear", 10)],
 }
@@ -174,7 +176,15 @@ def iteration(gen_params, clf, x, labels, R, z, c, kappa, dtype=torch.float64):
 
 def track(margins, dists, kappa):
     """The tracker on the sequences margins, dists [K, B, R] of the evaluated iterates (the last one is the final iterate):
-    (best_dist, best_margin, best_iter, best_row), each [B]."""
+    (best_dist, best_margin, best_iter, best_row), each [B].
+
+    Non-finite values:
+      - a row whose margin is NaN is never a success and never the smallest margin;
+      - a successful row whose distance is NaN is never taken (an image whose only successes have NaN distances has no success
+        and takes the no-success branch, where that row may well hold the smallest margin);
+      - if every margin of the final iterate is NaN, the result is row 0 (of the final iterate, best_iter = -1);
+      - +inf distances and margins compare as numbers (an +inf distance is taken while there is no success yet, an +inf margin is
+        the smallest only among +inf and NaN margins: the smallest r of the +inf ones)."""
     margins, dists = np.asarray(margins), np.asarray(dists)
     K, B, R = margins.shape
     bd, bm = np.empty(B, margins.dtype), np.empty(B, margins.dtype)
@@ -182,13 +192,16 @@ def track(margins, dists, kappa):
     for b in range(B):
         for k in range(K):
             for r in range(R):
-                if margins[k, b, r] < -kappa and (bi[b] < 0 or dists[k, b, r] < bd[b]):
-                    bd[b], bm[b], bi[b], br[b] = dists[k, b, r], margins[k, b, r], k, r
+                d = dists[k, b, r]
+                if margins[k, b, r] < -kappa and d == d and (bi[b] < 0 or d < bd[b]):
+                    bd[b], bm[b], bi[b], br[b] = d, margins[k, b, r], k, r
         if bi[b] < 0:
-            r = 0
-            for q in range(1, R):
-                if margins[K - 1, b, q] < margins[K - 1, b, r]:
+            r = -1
+            for q in range(R):
+                mq = margins[K - 1, b, q]
+                if mq == mq and (r < 0 or mq < margins[K - 1, b, r]):
                     r = q
+            r = max(r, 0)
             bd[b], bm[b], br[b] = dists[K - 1, b, r], margins[K - 1, b, r], r
     return bd, bm, bi, br
 
@@ -311,3 +324,210 @@ def attack_reference(seed):
     a = ATTACK
     gp, clf, x, labels, z0 = attack_inputs(seed)
     return run(gp, clf, x, labels, a["R"], z0, a["nb_iter"], lr=a["lr"], c=a["c"], kappa=a["kappa"])
+
+
+# ---------------------------------------------------------------------- many rows: selected, not searched (tests/test_gpu_latent_regimes.py)
+# A batch of 260 rows is never accepted whole by ``shares`` (its number of gates grows with the rows), but the attack has no
+# reduction across rows: a row's y, Z, m, d and dz depend on that row's (x_i, label_i, z_j) alone, so rows can be selected, as
+# generator_reference.draw_rows selects them for the generator's training step.
+# name -> latent, classifier kind, B, R, c, kappa, labels (None: drawn), classifier seed, draw seed.  The draw seed is the first one, at
+# classifier seed 0, for which the case is served within the pool cap AND float32 on the CPU uses at most MAX_SHARE of each bound
+# (find_case's rule; the margin's bound is the tight one: draw seeds 0, 1, 2 of lin2_3x3 measure 1.16, 1.01, 1.82 of it and seed 0 of
+# lin_130x2_l64 0.58 -- the float32 error of a logit, about 1e-6, against 1e-5 of a margin of a few tenths).  As found (one machine):
+# conv_4x65 0.009 / 0.112 / 0.016 of the dz / margin / dist bounds from a pool of 4 blocks, lin_130x2_l64 0.008 / 0.489 / 0.018 from
+# 9 blocks, lin2_3x3 0.010 / 0.479 / 0.013 from 2 blocks.  tests/test_latent_regimes_cpu.py re-checks each.
+REGIME_CASES = {
+    # row 256 = the first thread of the margin kernel's second workgroup, restart 61 of image 3; labels hold classes 0 and 9
+    "conv_4x65": dict(latent=128, kind="conv10", B=4, R=65, c=1.0, kappa=1.0, labels=(0, 5, 3, 9), clf_seed=0, seed=0),
+    # many images, few restarts
+    "lin_130x2_l64": dict(latent=64, kind="lin3", B=130, R=2, c=1.0, kappa=0.25, labels=None, clf_seed=0, seed=1),
+    # two classes
+    "lin2_3x3": dict(latent=128, kind="lin2", B=3, R=3, c=1.0, kappa=0.0, labels=(0, 1, 0), clf_seed=0, seed=3),
+}
+REGIME_STEPS = 2            # teacher-forced steps k = 0, 1
+
+
+def _row_eval(gp, clf, x_rows, lab_rows, z, c, kappa, dtype, want_dz=False):
+    """One forward (and, with want_dz, backward) of the rows z [n, latent] in ``dtype`` arithmetic: per-row nearest-to-zero
+    pre-activation of every ReLU layer (generator: Linear, Generator.2, Generator.3; then the classifier's), the signs' bytes, Z, m,
+    o, and dz.  The generator's layers are restated as generator_reference.preacts restates them; ``regime_case`` checks the y of
+    the selected rows against TorchGenerator.forward through ``iteration``."""
+    layers, cparams = clf
+    g = GR._gen(gp, dtype)
+    n = len(z)
+    zt = torch.as_tensor(np.asarray(z, np.float64)).to(dtype).clone().requires_grad_(want_dz)
+    gates = []
+    a = zt @ g.W + g.b
+    gates.append(a)
+    h = torch.relu(a).view(-1, 4, 4, g.W.shape[1] // 16).permute(0, 3, 1, 2)
+    for (w, b, used, act, _bn) in g.layers:
+        hin = h.shape[-1]
+        a = F.conv_transpose2d(h, w, bias=b, stride=2, padding=1)[..., :2 * hin, :2 * hin]
+        if act == "relu":
+            gates.append(a[..., :used, :used])
+            h = torch.relu(a)[..., :used, :used]
+        else:
+            h = torch.sigmoid(a)
+    y = h.permute(0, 2, 3, 1)
+    pre = []
+    Z = logits(layers, cparams, y, dtype, pre)
+    gates = [t.detach().double().numpy().reshape(n, -1) for t in gates] + [p.reshape(n, -1) for p in pre]
+    Zn = Z.detach().double().numpy()
+    m, o = margin_of(Zn, lab_rows)
+    out = {"gates": gates, "Z": Zn, "margin": m, "other": o, "y": y.detach().double().numpy()}
+    if want_dz:
+        idx = torch.arange(n)
+        xt = torch.as_tensor(np.asarray(x_rows, np.float64)).to(dtype)
+        mt = Z[idx, torch.as_tensor(np.asarray(lab_rows, np.int64))] - Z[idx, torch.as_tensor(o)]
+        d = ((y - xt) ** 2).reshape(n, -1).mean(dim=1)
+        active = torch.as_tensor((m + kappa > 0).astype(np.float64)).to(dtype)
+        (d + c * (mt + kappa) * active).sum().backward()
+        out["dz"] = zt.grad.double().numpy()
+    return out
+
+
+def _runner_up_gap(Z, lab_rows, o):
+    """Per row Z[o] - (the largest logit among the classes other than the label and o); +inf with two classes."""
+    Z = np.array(Z, np.float64)
+    rows = np.arange(len(Z))
+    top = Z[rows, o].copy()
+    Z[rows, lab_rows] = -np.inf
+    Z[rows, o] = -np.inf
+    return top - Z.max(axis=1)
+
+
+def regime_draw(name):
+    """(x [B,28,28,1], labels [B] int32, rs): the images and labels of a regime case and the stream its z blocks are drawn from."""
+    p = REGIME_CASES[name]
+    rs = np.random.RandomState(9000 + p["seed"])
+    x = (1.0 / (1.0 + np.exp(-rs.standard_normal((p["B"], 28, 28, 1))))).astype(np.float32)
+    n = KINDS[p["kind"]][-1][1]
+    labels = np.asarray(p["labels"], np.int32) if p["labels"] is not None else rs.randint(0, n, p["B"]).astype(np.int32)
+    return x, labels, rs
+
+
+def regime_scale(it, lab_rows):
+    """Per row what the margin's error is measured against: SCALAR_TOL |m| where the cancellation (|Z[label]| + |Z[o]|) / |m| is at
+    most MAX_CONDITION, MARGIN_ABS_TOL (|Z[label]| + |Z[o]|) otherwise (the two meet at MAX_CONDITION).  Returns (scale, absolute)."""
+    rows = np.arange(len(it["margin"]))
+    mag = np.abs(it["Z"][rows, lab_rows]) + np.abs(it["Z"][rows, it["other"]])
+    absolute = mag > MAX_CONDITION * np.abs(it["margin"])
+    return np.where(absolute, MARGIN_ABS_TOL * mag, SCALAR_TOL * np.abs(it["margin"])), absolute
+
+
+@functools.lru_cache(maxsize=None)
+def regime_case(name):
+    """The selected B x R batch of a regime case, its teacher-forced states and float64 iterations.
+
+    The pool grows by blocks of B R rows drawn at the projection's std from one stream; row q of a block is a candidate restart of
+    image q // R.  A candidate is judged at both teacher-forced steps: at z_0 = its draw and at z_1 = float32(Adam in float64 from
+    z_0 with the float64 dz).  It is kept when, at both,
+      - float64 and float32 on the CPU agree on every ReLU gate of the generator and the classifier, on o_j and on the sign of
+        m_j + kappa, and
+      - every float64 gate value lies farther from zero than ROW_MARGIN_FACTOR times the largest |float32 - float64| difference
+        of its layer over the pool (generator_reference._select_rows's rule); m_j + kappa is treated as one more gate with the
+        margins' differences, and Z[o] stands above the next other logit by more than ROW_MARGIN_FACTOR times twice the largest
+        logit difference.
+    Image i takes its first R kept candidates.  At most ROW_POOL_CAP blocks are drawn: this is a condition, not a tuning knob.
+
+    Returns gp, clf, x, labels, lab_rows, R, c, kappa, z / m / v [2] float32 (the states the device is given at k = 0, 1), its [2]
+    (``iteration`` in float64 at those float32 z), scale / absolute [2] (``regime_scale``), shares [3] (float32 on the CPU as
+    shares of the dz / margin / dist bounds, the worst over both steps), info (pool, blocks, kept, hinge_on [2])."""
+    p = REGIME_CASES[name]
+    B, R, c, kappa, latent = p["B"], p["R"], p["c"], p["kappa"], p["latent"]
+    N = B * R
+    gp, clf = GR.weights(latent, 64), classifier(p["kind"], p["clf_seed"])
+    x, labels, rs = regime_draw(name)
+    lab_rows = np.repeat(labels.astype(np.int64), R)
+    x_rows = np.repeat(x.astype(np.float64), R, axis=0)
+    zero = np.zeros((N, latent))
+    pool_z, near, agree, diffs = [], [], [], None
+    for blocks in range(1, GR.ROW_POOL_CAP + 1):
+        z0 = (rs.standard_normal((N, latent)) / np.sqrt(latent)).astype(np.float32)
+        a = _row_eval(gp, clf, x_rows, lab_rows, z0, c, kappa, torch.float64, want_dz=True)
+        z1 = CR.adam_update(z0.astype(np.float64), a["dz"], zero, zero, 1, LR, BETA1, BETA2)[0].astype(np.float32)
+        blk_near, blk_agree, blk_diff = [], np.ones(N, bool), []
+        for zk, a64 in ((z0, a), (z1, None)):
+            if a64 is None:
+                a64 = _row_eval(gp, clf, x_rows, lab_rows, zk, c, kappa, torch.float64)
+            a32 = _row_eval(gp, clf, x_rows, lab_rows, zk, c, kappa, torch.float32)
+            for g64, g32 in zip(a64["gates"], a32["gates"]):
+                blk_near.append(np.abs(g64).min(axis=1))
+                blk_diff.append(float(np.abs(g64 - g32).max()))
+                blk_agree &= ((g64 > 0) == (g32 > 0)).all(axis=1)
+            blk_near.append(np.abs(a64["margin"] + kappa))
+            blk_diff.append(float(np.abs(a64["margin"] - a32["margin"]).max()))
+            blk_near.append(_runner_up_gap(a64["Z"], lab_rows, a64["other"]))
+            blk_diff.append(2.0 * float(np.abs(a64["Z"] - a32["Z"]).max()))
+            blk_agree &= (a64["other"] == a32["other"]) & ((a64["margin"] + kappa > 0) == (a32["margin"] + kappa > 0))
+        pool_z.append(z0)
+        near.append(np.stack(blk_near))
+        agree.append(blk_agree)
+        # the two steps share one margin per layer
+        half = len(blk_diff) // 2
+        d = np.maximum(blk_diff[:half], blk_diff[half:])
+        diffs = d if diffs is None else np.maximum(diffs, d)
+        margins = GR.ROW_MARGIN_FACTOR * np.concatenate([diffs, diffs])
+        keep = np.stack(agree) & (np.stack(near) > margins[None, :, None]).all(axis=1)          # [blocks, N]
+        per_image = keep.reshape(blocks, B, R).transpose(1, 0, 2).reshape(B, blocks * R)         # image i: block-major candidates
+        if (per_image.sum(axis=1) >= R).all():
+            break
+    else:
+        raise AssertionError("%s: %d blocks of %d rows do not yield %d kept restarts for every image" % (name, GR.ROW_POOL_CAP, N, R))
+    zs = np.stack(pool_z).reshape(blocks, B, R, latent).transpose(1, 0, 2, 3).reshape(B, blocks * R, latent)
+    z0 = np.ascontiguousarray(np.stack([zs[i][np.flatnonzero(per_image[i])[:R]] for i in range(B)]).reshape(N, latent))
+    # the teacher-forced states and the float64 iterations, through ``iteration`` (TorchGenerator.forward, autograd)
+    it0 = iteration(gp, clf, x, labels, R, z0.astype(np.float64), c, kappa)
+    z1, m1, v1 = CR.adam_update(z0.astype(np.float64), it0["dz"], zero, zero, 1, LR, BETA1, BETA2)
+    z = [z0, z1.astype(np.float32)]
+    m = [np.zeros((N, latent), np.float32), m1.astype(np.float32)]
+    v = [np.zeros((N, latent), np.float32), v1.astype(np.float32)]
+    its = [it0, iteration(gp, clf, x, labels, R, z[1].astype(np.float64), c, kappa)]
+    assert np.abs(its[0]["y"] - _row_eval(gp, clf, x_rows, lab_rows, z0, c, kappa, torch.float64)["y"]).max() <= 1e-12
+    scale, absolute, worst, hinge_on = [], [], np.zeros(3), []
+    for k in range(REGIME_STEPS):
+        a, b = its[k], iteration(gp, clf, x, labels, R, z[k].astype(np.float64), c, kappa, torch.float32)
+        for g64, g32 in zip(a["gates"], b["gates"]):
+            assert ((g64 > 0) == (g32 > 0)).all(), "the selected rows disagree on a gate"
+        assert (a["other"] == b["other"]).all() and ((a["margin"] + kappa > 0) == (b["margin"] + kappa > 0)).all()
+        s, ab = regime_scale(a, lab_rows)
+        scale.append(s)
+        absolute.append(ab)
+        hinge_on.append(int((a["margin"] + kappa > 0).sum()))
+        worst = np.maximum(worst, [np.abs(a["dz"] - b["dz"]).max() / (DZ_TOL * np.abs(a["dz"]).max()),
+                                   (np.abs(a["margin"] - b["margin"]) / s).max(),
+                                   (np.abs(a["dist"] - b["dist"]) / (SCALAR_TOL * np.abs(a["dist"]))).max()])
+    info = {"pool": blocks * N, "blocks": blocks, "kept": float(keep.mean()), "hinge_on": hinge_on,
+            "absolute": [int(ab.sum()) for ab in absolute]}
+    return {"gp": gp, "clf": clf, "x": x, "labels": labels, "lab_rows": lab_rows, "R": R, "c": c, "kappa": kappa, "z": z, "m": m, "v": v,
+            "its": its, "scale": scale, "absolute": absolute, "shares": tuple(float(w) for w in worst), "info": info}
+
+
+# ---------------------------------------------------------------------- the tracker past 64 restarts
+# B = 3 images of the 10-class classifier (seed 0), R restarts.  The synthetic generator's images all fall into one class (4, with
+# margins of 0.2 to 1.0 at the draw), so the labels decide the branch: image 0 (label 1, margins -1.0 .. -0.2 at the draw) has a
+# few successes at kappa 0.9 and gains more as the hinge pushes; image 1 (label 4) cannot reach m < -0.9 in three small steps and
+# stays on the no-success branch; image 2 (label 7, margins below -1.9) succeeds in every row, and its LAST restart starts at the z
+# its x was generated from, so that its distance is the smallest by orders of magnitude: a winner at r = R - 1 >= 64.
+TRACKER = dict(latent=128, kind="conv10", clf_seed=0, B=3, labels=(1, 4, 7), nb_iter=3, lr=0.01, c=2.0, kappa=0.9)
+
+
+@functools.lru_cache(maxsize=None)
+def tracker_inputs(R):
+    """(gp, clf, x [3,28,28,1], labels [3], z0 [3 R, latent]) of the R > 64 tracker case."""
+    t = TRACKER
+    gp, clf = GR.weights(t["latent"], 64), classifier(t["kind"], t["clf_seed"])
+    rs = np.random.RandomState(9500 + R)
+    x = (1.0 / (1.0 + np.exp(-rs.standard_normal((t["B"], 28, 28, 1))))).astype(np.float32)
+    z_true = (rs.standard_normal((1, t["latent"])) / np.sqrt(t["latent"])).astype(np.float32)
+    z0 = (rs.standard_normal((t["B"] * R, t["latent"])) / np.sqrt(t["latent"])).astype(np.float32)
+    x[2] = GR._gen(gp, torch.float64).forward(torch.as_tensor(z_true.astype(np.float64))).numpy()[0].astype(np.float32)
+    z0[3 * R - 1] = z_true[0]
+    return gp, clf, x, np.asarray(t["labels"], np.int32), z0
+
+
+@functools.lru_cache(maxsize=None)
+def tracker_reference(R):
+    t = TRACKER
+    gp, clf, x, labels, z0 = tracker_inputs(R)
+    return run(gp, clf, x, labels, R, z0, t["nb_iter"], lr=t["lr"], c=t["c"], kappa=t["kappa"])
