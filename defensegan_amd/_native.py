@@ -82,6 +82,8 @@ SYMBOLS = [
     ("dg_gen_set_adam", _i, [_vp, _cp, _vp, _vp, _i64, _i]),
     ("dg_latent_attack", _i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _i64, _i, _f, _f, _f, _f, _f, _vp, _vp, _i64, _i,
                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dg_spsa_queries", _i, [_vp, _i, _i64, _i, _f, _u64, _i64, _i, _f, _f, _vp, _vp]),
+    ("dg_spsa_step", _i, [_vp, _vp, _i, _i, _i64, _i, _f, _u64, _i64, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

@@ -36,13 +36,6 @@ void bpda_release(BpdaWork* w) {
 
 namespace {
 
-__device__ __forceinline__ float bpda_next(float g, float xc, float xo, float eps, float eps_iter, float lo, float hi) {
-    const float sgn = g > 0.f ? 1.f : (g < 0.f ? -1.f : 0.f);
-    float d = (xc + eps_iter * sgn) - xo;
-    d = d < -eps ? -eps : (d > eps ? eps : d);
-    return clf_clip(xo + d, lo, hi);
-}
-
 // The step, elementwise over V-wide vectors (V = 4: float4 loads and stores; V = 1 where H W C is no multiple of 4 or a
 // pointer is not 16-byte aligned).  accumulate_only: gsum += g.  Otherwise t = gsum + g (t = g when gsum == NULL) and
 // x_next = the projected sign step of t.  HBM-bound: three reads (g, x_cur, x_orig; with gsum a fourth) and one write of 4 bytes
@@ -66,10 +59,10 @@ __global__ __launch_bounds__(256) void bpda_step_kernel(const float* __restrict_
         const float4 xc = reinterpret_cast<const float4*>(x_cur)[i];
         const float4 xo = reinterpret_cast<const float4*>(x_orig)[i];
         float4 o;
-        o.x = bpda_next(t.x, xc.x, xo.x, eps, eps_iter, lo, hi);
-        o.y = bpda_next(t.y, xc.y, xo.y, eps, eps_iter, lo, hi);
-        o.z = bpda_next(t.z, xc.z, xo.z, eps, eps_iter, lo, hi);
-        o.w = bpda_next(t.w, xc.w, xo.w, eps, eps_iter, lo, hi);
+        o.x = clf_sign_step(t.x, xc.x, xo.x, eps, eps_iter, lo, hi);
+        o.y = clf_sign_step(t.y, xc.y, xo.y, eps, eps_iter, lo, hi);
+        o.z = clf_sign_step(t.z, xc.z, xo.z, eps, eps_iter, lo, hi);
+        o.w = clf_sign_step(t.w, xc.w, xo.w, eps, eps_iter, lo, hi);
         reinterpret_cast<float4*>(x_next)[i] = o;
     } else {
         float t = g[i];
@@ -78,7 +71,7 @@ __global__ __launch_bounds__(256) void bpda_step_kernel(const float* __restrict_
             gsum[i] = t;
             return;
         }
-        x_next[i] = bpda_next(t, x_cur[i], x_orig[i], eps, eps_iter, lo, hi);
+        x_next[i] = clf_sign_step(t, x_cur[i], x_orig[i], eps, eps_iter, lo, hi);
     }
 }
 

@@ -133,11 +133,18 @@ void train_launch_wgrad(const ClfLayer& v, const float* x, const float* g, const
 // and the step count.  Fetch them per call: adding a layer moves them.
 int train_adam_state(dg_clf* h, float*** m, float*** v, long long** t);
 
-// ---- shared by the attack steps (dg_bpda.hip, dg_ball.hip) -------------------------------------------------------------------------
+// ---- shared by the attack steps (dg_bpda.hip, dg_ball.hip, dg_spsa.hip) -------------------------------------------------------------------------
 // the final clip of every attack step: clip(v, lo, hi) with lo <= hi
 __device__ __forceinline__ float clf_clip(float v, float lo, float hi) {
     v = v < lo ? lo : v;
     return v > hi ? hi : v;
+}
+// the projected sign step of one element: clip(xo + clamp(xc + eps_iter sign(g) - xo, -eps, eps), lo, hi), sign(0) = sign(NaN) = 0
+__device__ __forceinline__ float clf_sign_step(float g, float xc, float xo, float eps, float eps_iter, float lo, float hi) {
+    const float sgn = g > 0.f ? 1.f : (g < 0.f ? -1.f : 0.f);
+    float d = (xc + eps_iter * sgn) - xo;
+    d = d < -eps ? -eps : (d > eps ? eps : d);
+    return clf_clip(xo + d, lo, hi);
 }
 // whether float4 may be used on p (NULL counts as aligned: an absent operand)
 inline bool clf_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }

@@ -743,10 +743,9 @@ def bpda_seed_schedule(seed: int, nb_iter: int, eot_samples: int):
     return [[int(seed) + k * m + s for s in range(m)] for k in range(int(nb_iter))], int(seed) + int(nb_iter) * m
 
 
-class BpdaDeviceOps(object):
-    """The device operations ``BPDA.generate`` is made of (``step_ball`` and ``dist`` only with ``ord = 2``), on tensors of the classifier's device and torch's current stream;
-    none of them waits for the device.  (``BPDA`` takes any object with these methods and a ``device``: the tests drive the loop
-    with a recording stand-in.)"""
+class _AttackDeviceOps(object):
+    """What the device operations of the iterative attacks on a (defended) model share: the classifier, its projection's model (or
+    None), the device; the prediction on a batch; the best tracking."""
 
     def __init__(self, model: MLP):
         import torch
@@ -756,13 +755,29 @@ class BpdaDeviceOps(object):
         self.model, self.gan = model, (model.rec_layer.rec_model if model.rec_layer is not None else None)
         self.device = torch.device("cuda", model._device)
 
-    def project(self, x, seed, first_row):
-        """gan.reconstruct: latents drawn as dg_init_latents does for (seed, first_row + row)."""
-        return self.gan.reconstruct(x, seed=int(seed), first_row=int(first_row))
-
     def predict(self, rec):
         """[B] int32: the classifier's first argmax on ``rec`` (dg_eval_batch)."""
         return self.model.eval_batch(rec, None, None, sync=False)[1]
+
+    def track(self, preds, labels, k, x_iter, x_best, first_success):
+        """dg_bpda_track: images still without a success take iterate k as their best, and k as their first success where
+        ``preds != labels``."""
+        import torch
+        B = int(preds.shape[0])
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().dg_bpda_track(
+                preds.data_ptr(), labels.data_ptr(), B, int(k), x_iter.data_ptr(), x_best.data_ptr(), first_success.data_ptr(),
+                int(x_iter.numel() // B), torch.cuda.current_stream(self.device).cuda_stream))
+
+
+class BpdaDeviceOps(_AttackDeviceOps):
+    """The device operations ``BPDA.generate`` is made of (``step_ball`` and ``dist`` only with ``ord = 2``), on tensors of the classifier's device and torch's current stream;
+    none of them waits for the device.  (``BPDA`` takes any object with these methods and a ``device``: the tests drive the loop
+    with a recording stand-in.)  ``predict`` and ``track`` are the base class's."""
+
+    def project(self, x, seed, first_row):
+        """gan.reconstruct: latents drawn as dg_init_latents does for (seed, first_row + row)."""
+        return self.gan.reconstruct(x, seed=int(seed), first_row=int(first_row))
 
     def step(self, rec, labels, x_cur, x_orig, gsum, accumulate_only, eps, eps_iter, clip_min, clip_max, x_next):
         """dg_bpda_step: the classifier's input gradient at ``rec``, then ``gsum += g`` (accumulate_only) or the projected sign
@@ -788,16 +803,6 @@ class BpdaDeviceOps(object):
     def dist(self, x_adv, x_orig):
         """dg_row_norms: [n] float32, the per-image L2 distance of ``x_adv`` from ``x_orig``."""
         return _row_norms(x_adv, x_orig, 2)
-
-    def track(self, preds, labels, k, x_iter, x_best, first_success):
-        """dg_bpda_track: images still without a success take iterate k as their best, and k as their first success where
-        ``preds != labels``."""
-        import torch
-        B = int(preds.shape[0])
-        with torch.cuda.device(self.device):
-            _native.check(_native.load().dg_bpda_track(
-                preds.data_ptr(), labels.data_ptr(), B, int(k), x_iter.data_ptr(), x_best.data_ptr(), first_success.data_ptr(),
-                int(x_iter.numel() // B), torch.cuda.current_stream(self.device).cuda_stream))
 
 
 class BPDA(object):
@@ -1016,6 +1021,174 @@ class ProjectedGradientDescent(object):
         if was_numpy:
             x_adv, info = x_adv.cpu().numpy(), tuple(v.cpu().numpy() for v in info)
         return (x_adv,) + info if return_info else x_adv
+
+
+# ---------------------------------------------------------------------- the score-based black-box attack: SPSA
+class SpsaDeviceOps(_AttackDeviceOps):
+    """The device operations ``SPSA.generate`` is made of, on tensors of the classifier's device and torch's current stream; none
+    of them waits for the device.  (``SPSA`` takes any object with these methods and a ``device``: the tests drive the loop with a
+    recording stand-in.)  ``predict`` and ``track`` are the base class's."""
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def queries(self, x_cur, n, delta, seed, first_image, k, clip_min, clip_max, q):
+        """dg_spsa_queries: the 2 n + 1 queries of every image of ``x_cur`` [B, ...] into ``q`` [B (2 n + 1), ...]."""
+        import torch
+        B = int(x_cur.shape[0])
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().dg_spsa_queries(
+                x_cur.data_ptr(), B, int(x_cur.numel() // B), int(n), float(delta), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image), int(k),
+                float(clip_min), float(clip_max), q.data_ptr(), self._stream()))
+
+    def project(self, q, seed, first_row, row_step=None):
+        """The defended model's projection of ``q``: row j takes the latents ``first_row + j * row_step + r``, r < rec_rr, of the
+        stream of ``seed``.  ``row_step`` None = rec_rr, consecutive rows: one ``gan.reconstruct``; any other step (the closing
+        pass, whose images lie 2 n + 1 queries apart) draws each row's latents with ``init_latents`` and hands them over as z0 --
+        the values ``reconstruct`` would have drawn.  On a bare model: the identity."""
+        import torch
+        if self.gan is None:
+            return q
+        R = int(self.gan.rec_rr)
+        if row_step is None or int(row_step) == R or int(q.shape[0]) == 1:
+            return self.gan.reconstruct(q, seed=int(seed), first_row=int(first_row))
+        z0 = torch.cat([self.gan.init_latents(R, seed=int(seed), first_row=int(first_row) + j * int(row_step)) for j in range(int(q.shape[0]))])
+        return self.gan.reconstruct(q, z_init_val=z0, seed=int(seed))
+
+    def logits(self, rec):
+        """[B, classes] float32: the classifier's logits on ``rec`` (dg_clf_forward)."""
+        import torch
+        B = int(rec.shape[0])
+        out = torch.empty(B, self.model.nb_classes, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().dg_clf_forward(self.model._handle, rec.data_ptr(), B, out.data_ptr(), None, self._stream()))
+        return out
+
+    def step(self, logits, labels, n, delta, seed, first_image, k, x_cur, x_orig, eps, eps_iter, clip_min, clip_max, x_next, out_grad=None):
+        """dg_spsa_step: margins, the estimate and the projected sign step from ``x_cur`` around ``x_orig`` into ``x_next``."""
+        import torch
+        B = int(x_cur.shape[0])
+        with torch.cuda.device(self.device):
+            _native.check(_native.load().dg_spsa_step(
+                logits.data_ptr(), labels.data_ptr(), B, int(logits.shape[1]), int(x_cur.numel() // B), int(n), float(delta),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image), int(k), x_cur.data_ptr(), x_orig.data_ptr(), float(eps), float(eps_iter),
+                float(clip_min), float(clip_max), x_next.data_ptr(), out_grad.data_ptr() if out_grad is not None else None, self._stream()))
+
+
+class SPSA(object):
+    """The score-based black-box attack: SPSA (Uesato et al. 2018) with Rademacher directions and the projected sign step of
+    ``ProjectedGradientDescent`` and ``BPDA``, L-infinity.  It reads only the attacked model's logits, so it attacks the DEFENDED
+    model (``add_rec_model``), whose gradient is identically zero (_REC_GRADIENT_NOTE), as well as a bare classifier, where the
+    identity stands in for the projection.  Not in the reference.  With ``n = spsa_samples``, ``g`` an image's index in ``x``:
+
+        x_0 = clip(x)
+        for k < nb_iter:   u_i[e] = +-1 by bit (i & 31) of word (e & 3) of Philox4x32-10(key = seed, counter = (e >> 2, g,
+                                    k ceil(n / 32) + (i >> 5), 0x53505341))                                            i < n
+                           q_0 = x_k,  q+_i = clip(x_k + delta u_i),  q-_i = clip(x_k - delta u_i)     (2 n + 1 queries, clipped)
+                           L(q) = max_{j != y} Z_j - Z_y  on the logits Z of the model (through the projection) at q
+                           ghat = (1 / (2 delta n)) sum_i (L(q+_i) - L(q-_i)) u_i          (float32, ascending i; dg_spsa_step)
+                           x_{k+1} = clip(x + clamp(x_k + eps_iter sign(ghat) - x, -eps, eps), clip_min, clip_max),  sign(0) = 0
+
+    A label outside [0, classes) gives L = 0 and a zero step; a pair whose loss difference is not finite contributes 0.  Best
+    tracking as BPDA's: iterate j = 1 .. nb_iter succeeds when the model's first arg-max on ITS query 0 is not ``y`` (iteration j's
+    query 0 is x_j; iterate nb_iter is judged by one closing query per image); ``generate`` returns per image the first successful
+    iterate, or else the last one.  ``return_info=True`` adds ``first_success`` [n] int32 (1 .. nb_iter, or -1) and ``queries``,
+    the queries spent per image: ``nb_iter * (2 n + 1) + 1``.
+
+    Defended model: iteration k projects with latent seed ``seed + k``, the closing pass with ``seed + nb_iter``; the latents of
+    query c of image g are rows ``(g (2 n + 1) + c) rec_rr + r`` of that stream.  ``batch_size`` (default: the reconstruction
+    layer's, else all) bounds the images whose queries are alive at once, and their flat query range is cut into engine calls by
+    ``gan_defense.engine_step``; every row of the engine and every element of the two kernels is computed independently of its
+    batch, so the result depends on neither, bit for bit.  On a bare model no latent seeds are used.
+
+    ``x`` NumPy or a device tensor [n, H, W, C] (NumPy in gives NumPy out; a tensor gives tensors on the caller's current stream,
+    not waited for); ``y`` class indices or one-hot rows, required.  ``seed`` defaults to BPDA_DEFAULT_SEED.  No host read is made
+    inside the attack.  A reconstruction layer with a fixed ``z_init`` is a ValueError (every projection draws fresh latents); a
+    USE_BN generator a NotImplementedError (its batch statistics would couple an image's queries to the cut)."""
+
+    def __init__(self, model: MLP, back="tf", sess=None, ops=None):
+        self.model = model
+        self._ops = ops
+
+    def generate(self, x, y, eps=0.3, eps_iter=0.05, nb_iter=10, spsa_samples=32, delta=0.01, clip_min=None, clip_max=None, seed=None,
+                 batch_size=None, return_info=False):
+        import torch
+        from . import gan_defense
+        m = self.model
+        rl = m.rec_layer
+        gan = rl.rec_model if rl is not None else None
+        if rl is not None and rl.z_init is not None:
+            raise ValueError("SPSA draws fresh latents for every projection; the reconstruction layer has a fixed z_init")
+        if gan is not None and bool(getattr(gan, "use_bn", False)):
+            raise NotImplementedError("SPSA on a USE_BN generator: its batch statistics would couple an image's queries to how the "
+                                      "engine calls are cut")
+        nb_iter, ns = int(nb_iter), int(spsa_samples)
+        if nb_iter < 1:
+            raise ValueError("nb_iter must be >= 1, got %d" % nb_iter)
+        if ns < 1:
+            raise ValueError("spsa_samples must be >= 1, got %d" % ns)
+        if not float(delta) > 0:
+            raise ValueError("delta must be > 0")
+        if not (float(eps) >= 0 and float(eps_iter) >= 0):
+            raise ValueError("eps and eps_iter must be >= 0")
+        lo = float("-inf") if clip_min is None else float(clip_min)
+        hi = float("inf") if clip_max is None else float(clip_max)
+        if not lo <= hi:
+            raise ValueError("clip_min must not exceed clip_max")
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        seed = BPDA_DEFAULT_SEED if seed is None else int(seed)
+        ops = self._ops if self._ops is not None else SpsaDeviceOps(m)
+        dev = ops.device
+        was_numpy = isinstance(x, np.ndarray)
+        t = (torch.from_numpy(np.ascontiguousarray(x, np.float32)) if was_numpy else x).to(device=dev, dtype=torch.float32).contiguous()
+        if t.dim() != 4 or tuple(t.shape[1:]) != tuple(m.input_shape[1:]) or int(t.shape[0]) == 0:
+            raise ValueError("x must be [n, %s] with n > 0, got %s" % (", ".join(str(d) for d in m.input_shape[1:]), tuple(t.shape)))
+        n = int(t.shape[0])
+        yy = np.asarray(y if isinstance(y, np.ndarray) else (y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y))
+        if yy.ndim > 1:
+            yy = yy.argmax(axis=-1)                                # one-hot labels as cleverhans takes them
+        if yy.shape != (n,):
+            raise ValueError("y must be %d class indices or one-hot rows" % n)
+        lab = torch.from_numpy(np.ascontiguousarray(yy.astype(np.int32))).to(dev)
+        Q = 2 * ns + 1                                             # queries per image and iteration
+        R = int(gan.rec_rr) if gan is not None else 1
+        bs = min(n, int(batch_size or (rl.batch_size if rl is not None else None) or n))
+        chunks = [(a, min(n, a + bs)) for a in range(0, n, bs)]
+
+        def cuts(count):
+            """An engine call's share [c0, c1) of ``count`` consecutive rows; a bare model takes them in one."""
+            step = gan_defense.engine_step(gan.reconstruct, 1, R, count) if gan is not None else count
+            return [(c0, min(count, c0 + step)) for c0 in range(0, count, step)]
+
+        x_cur = torch.clamp(t, lo, hi)
+        x_next, x_best = torch.empty_like(x_cur), torch.empty_like(x_cur)
+        first_success = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        q = torch.empty((bs * Q,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+        for k in range(nb_iter):
+            for a, b in chunks:
+                nq = (b - a) * Q
+                ops.queries(x_cur[a:b], ns, delta, seed, a, k, lo, hi, q[:nq])
+                Z, rec0 = [], []
+                for c0, c1 in cuts(nq):
+                    rec = ops.project(q[c0:c1], (seed + k) if gan is not None else None, (a * Q + c0) * R)
+                    Z.append(ops.logits(rec))
+                    if k > 0 and -c0 % Q < c1 - c0:                # the cut holds query 0 of an image: the defended view of iterate k
+                        rec0.append(rec[-c0 % Q::Q])
+                if k > 0:
+                    ops.track(ops.predict(rec0[0] if len(rec0) == 1 else torch.cat(rec0)), lab[a:b], k, x_cur[a:b], x_best[a:b],
+                              first_success[a:b])
+                ops.step(Z[0] if len(Z) == 1 else torch.cat(Z), lab[a:b], ns, delta, seed, a, k, x_cur[a:b], t[a:b], eps, eps_iter, lo, hi,
+                         x_next[a:b])
+            x_cur, x_next = x_next, x_cur
+        for a, b in chunks:                                        # the closing query of every image judges iterate nb_iter
+            preds = [ops.predict(ops.project(x_cur[a + c0:a + c1], (seed + nb_iter) if gan is not None else None, (a + c0) * Q * R, Q * R))
+                     for c0, c1 in cuts(b - a)]
+            ops.track(preds[0] if len(preds) == 1 else torch.cat(preds), lab[a:b], nb_iter, x_cur[a:b], x_best[a:b], first_success[a:b])
+        if not return_info:
+            return x_best.cpu().numpy() if was_numpy else x_best
+        return (x_best.cpu().numpy() if was_numpy else x_best), (first_success.cpu().numpy() if was_numpy else first_success), nb_iter * Q + 1
 
 
 def rand_fgsm_prestep(test_images, eps: float, alpha: float, min_val: float = 0.0, max_val: float = 1.0, rng=None):

@@ -3,7 +3,7 @@ device:
 
     whitebox    trains the classifier (cleverhans model_train; ``adv_tr`` adds FGSM inputs; ``train_on_recs`` trains on cached
                 reconstructions), attacks the ORIGINAL test images (fgsm, rand_fgsm, cw -- and pgd on a bare model, bpda and latent
-                on a defended one, which the reference has not) and measures the accuracy on the adversarial images, through the
+                on a defended one, spsa on either, which the reference has not) and measures the accuracy on the adversarial images, through the
                 Defense-GAN projection for ``defense_gan`` (with the ROC triple)                       whitebox.py:56-233
     main        the flags and the result files of whitebox.py:236-392
 
@@ -12,6 +12,8 @@ device:
         --defense_type defense_gan --attack_type bpda --results_dir run0
     python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --init_path output/gans/mnist \\
         --defense_type defense_gan --attack_type latent --latent_iters 100 --rec_rr 10
+    python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --init_path output/gans/mnist \\
+        --defense_type defense_gan --attack_type spsa --spsa_samples 32 --spsa_delta 0.01 --num_tests 100
 
 Kept from the reference: ``RandomState([11, 24, 1990])`` for the training schedule; the clean accuracy on the (reconstructed) test
 split printed after every epoch; with ``defense_gan`` the reconstruction layer is attached AFTER training and BEFORE the attack
@@ -27,12 +29,14 @@ import numpy as np
 from . import config, datasets, gan_defense, network_builder, py2pickle, utils_tf
 from .blackbox import SEED, _Phase, _accuracy, _labels, load_recs, result_path
 
-ATTACKS = ("fgsm", "cw", "pgd", "bpda", "latent")
+ATTACKS = ("fgsm", "cw", "pgd", "bpda", "latent", "spsa")
 # whitebox.py:203-209; 'feed' is TensorFlow's business
 CW_PARAMS = {"binary_search_steps": 1, "max_iterations": 100, "learning_rate": 10.0, "initial_const": 100}
 ITERATIVE_DEFAULTS = {"eps_iter": 0.05, "nb_iter": 10, "eot_samples": 1}
 # the latent-space attack (network_builder.LatentAttack): Adam steps on z, their learning rate, the weight of the classification term
 LATENT_DEFAULTS = {"latent_iters": 100, "latent_lr": 0.05, "latent_c": 1.0}
+# the score-based black-box attack (network_builder.SPSA): direction pairs per iteration and the probe size; eps_iter and nb_iter as pgd's
+SPSA_DEFAULTS = {"spsa_samples": 32, "spsa_delta": 0.01}
 PGD_CALL_IMAGES = 10000                       # images per dg_pgd call: bounds the kept activations, not the result
 
 
@@ -46,33 +50,36 @@ def attack_kind(attack_type):
     if "fgsm" in t:
         return "fgsm", rand
     base = t.replace("rand", "").strip("_+")
-    if base in ATTACKS and not (rand and base in ("cw", "latent")):
+    if base in ATTACKS and not (rand and base in ("cw", "latent", "spsa")):
         return base, rand
-    raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, pgd (defense_type none / adv_tr), bpda or latent (defense_gan)" % (attack_type,))
+    raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, pgd (defense_type none / adv_tr), bpda or latent (defense_gan), spsa" % (attack_type,))
 
 
 def attack_ord_value(attack_ord, kind=None):
     """``attack_ord`` (np.inf, 1, 2 or their names 'inf', '1', '2') as np.inf or an int, checked against the attack ``kind``: fgsm
     takes 1 and 2 (``FastGradientMethod``'s ord), pgd and bpda take 2 (1 is NotImplementedError: the L1 projection needs a sort), cw
-    is an L2 attack already and takes none."""
+    is an L2 attack already and takes none, as do latent and spsa."""
     who = "attack_ord" if kind is None else "attack_ord with attack_type %s" % kind
-    allowed = {"fgsm": (np.inf, 1, 2), "pgd": (np.inf, 2), "bpda": (np.inf, 2), "cw": (np.inf,), "latent": (np.inf,)}.get(kind, (np.inf, 1, 2))
+    allowed = {"fgsm": (np.inf, 1, 2), "pgd": (np.inf, 2), "bpda": (np.inf, 2), "cw": (np.inf,), "latent": (np.inf,), "spsa": (np.inf,)}.get(kind, (np.inf, 1, 2))
     return network_builder._attack_ord(attack_ord, allowed, who)
 
 
 def _attack_params(kind, attack_params):
     """The overrides ``attack_params`` holds for this attack: eps_iter / nb_iter (pgd, bpda), eot_samples (bpda), any
-    CarliniWagnerL2 parameter (cw), latent_iters / latent_lr / latent_c (latent).  Values of None and the iterative attacks' keys given to another attack are left out."""
+    CarliniWagnerL2 parameter (cw), latent_iters / latent_lr / latent_c (latent), eps_iter / nb_iter / spsa_samples / spsa_delta (spsa).  Values of None and the iterative attacks' keys given to another attack are left out."""
     given = {k: v for k, v in (attack_params or {}).items() if v is not None}
-    known = set(ITERATIVE_DEFAULTS) | set(network_builder.CarliniWagnerL2.DEFAULTS) | set(LATENT_DEFAULTS)
+    known = set(ITERATIVE_DEFAULTS) | set(network_builder.CarliniWagnerL2.DEFAULTS) | set(LATENT_DEFAULTS) | set(SPSA_DEFAULTS)
     if set(given) - known:
         raise ValueError("unknown attack_params: %s" % sorted(set(given) - known))
     if kind == "cw":
         return {k: v for k, v in given.items() if k in network_builder.CarliniWagnerL2.DEFAULTS}
     if kind == "latent":
         return {k: given.get(k, d) for k, d in LATENT_DEFAULTS.items()}
-    keys = {"pgd": ("eps_iter", "nb_iter"), "bpda": ("eps_iter", "nb_iter", "eot_samples")}.get(kind, ())
-    return {k: given.get(k, ITERATIVE_DEFAULTS[k]) for k in keys}
+    keys = {"pgd": ("eps_iter", "nb_iter"), "bpda": ("eps_iter", "nb_iter", "eot_samples"), "spsa": ("eps_iter", "nb_iter")}.get(kind, ())
+    out = {k: given.get(k, ITERATIVE_DEFAULTS[k]) for k in keys}
+    if kind == "spsa":
+        out.update({k: given.get(k, d) for k, d in SPSA_DEFAULTS.items()})
+    return out
 
 
 def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate=0.001, nb_epochs=10, eps=0.3, alpha=0.05,
@@ -98,6 +105,9 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
       bpda              BPDA on the true labels: 'defense_gan' only
       latent            LatentAttack on the true labels, ``gan.rec_rr`` restarts per image: 'defense_gan' only.  x_adv = G(z) lies in
                         the generator's range, not in the ``eps`` ball; ``attack_params`` latent_iters (100), latent_lr (0.05), latent_c (1)
+      spsa              SPSA on the true labels, from the model's logits alone: any defense type (with 'defense_gan' every query goes
+                        through the projection: nb_iter (2 spsa_samples + 1) + 1 projections per image); ``attack_params`` eps_iter,
+                        nb_iter, spsa_samples (32), spsa_delta (0.01)
     ``attack_params`` overrides ``eps_iter`` (0.05), ``nb_iter`` (10), ``eot_samples`` (1) of pgd / bpda and any CarliniWagnerL2
     parameter.  pgd with 'defense_gan' or bpda without it is a ValueError.  ``attack_ord`` (default np.inf): 2 runs pgd / bpda in an
     L2 ball of radius ``eps`` (their ``ord``), 1 or 2 runs fgsm / rand_fgsm as FGM with that norm; 1 with pgd / bpda is
@@ -131,8 +141,8 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
         if kind[0] == "latent" and not defended:
             raise ValueError("attack_type latent searches the generator's range and needs the projection (defense_type defense_gan), "
                              "not %s" % defense_type)
-        if kind[0] == "bpda" and same_init:
-            raise ValueError("attack_type bpda draws fresh latents for every projection: not with same_init")
+        if kind[0] in ("bpda", "spsa") and same_init:
+            raise ValueError("attack_type %s draws fresh latents for every projection: not with same_init" % kind[0])
         extra = _attack_params(kind[0], attack_params)
         attack_ord = attack_ord_value(attack_ord, kind[0])
         if attack_ord != np.inf and kind[0] in ("pgd", "bpda"):
@@ -208,6 +218,11 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
             attack = network_builder.LatentAttack(model, gan)
             x_adv = attack.generate(test_adv_from, test_labels, rec_rr=int(gan.rec_rr), nb_iter=int(extra["latent_iters"]),
                                     learning_rate=float(extra["latent_lr"]), c=float(extra["latent_c"]), seed=seed, batch_size=batch_size)
+        elif kind == "spsa":
+            attack = network_builder.SPSA(model)
+            x_adv = attack.generate(test_adv_from, test_labels, eps=eps, eps_iter=extra["eps_iter"], nb_iter=extra["nb_iter"],
+                                    spsa_samples=int(extra["spsa_samples"]), delta=float(extra["spsa_delta"]), clip_min=min_val, clip_max=1.0,
+                                    seed=seed, batch_size=batch_size)
         else:
             attack = network_builder.BPDA(model)
             x_adv = attack.generate(test_adv_from, test_labels, eps=eps, clip_min=min_val, clip_max=1.0, seed=seed, batch_size=batch_size,
@@ -284,7 +299,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--random_test_iter", type=int, default=-1, help="accepted and ignored, as in the reference")
     ap.add_argument("--online_training", action="store_true", help="not implemented (NotImplementedError)")
     ap.add_argument("--defense_type", default="none", choices=["none", "defense_gan", "adv_tr"], help="Type of defense")
-    ap.add_argument("--attack_type", default="none", help="Type of attack [fgsm|cw|rand_fgsm|pgd|bpda|latent]; none: train and stop")
+    ap.add_argument("--attack_type", default="none", help="Type of attack [fgsm|cw|rand_fgsm|pgd|bpda|latent|spsa]; none: train and stop")
     ap.add_argument("--results_dir", default=None, help="The final subdirectory of the results.")
     ap.add_argument("--model", default="F", choices=sorted(network_builder.MODELS), help="The classifier model.")
     ap.add_argument("--debug_dir", default="temp", help="accepted and ignored (the reference's qualitative debug output)")
@@ -294,6 +309,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eps_iter", type=float, default=None, help="pgd / bpda step size (default 0.05)")
     ap.add_argument("--nb_iter", type=int, default=None, help="pgd / bpda iterations (default 10)")
     ap.add_argument("--eot_samples", type=int, default=None, help="bpda: projections the gradient is summed over per iteration (default 1)")
+    ap.add_argument("--spsa_samples", type=int, default=None, help="spsa: direction pairs per iteration (default 32): 2 of them + 1 queries per image")
+    ap.add_argument("--spsa_delta", type=float, default=None, help="spsa: probe size of the finite difference (default 0.01)")
     ap.add_argument("--latent_iters", type=int, default=None, help="latent: Adam steps on z (default 100); --rec_rr is its restarts per image")
     ap.add_argument("--latent_lr", type=float, default=None, help="latent: Adam's learning rate (default 0.05)")
     ap.add_argument("--latent_c", type=float, default=None, help="latent: weight of the classification term (default 1)")
@@ -345,7 +362,8 @@ def main(argv=None) -> int:
                           defense_type=args.defense_type, num_tests=args.num_tests, num_train=args.num_train,
                           fgsm_eps_tr=args.fgsm_eps_tr, same_init=args.same_init, recs=recs,
                           attack_params={"eps_iter": args.eps_iter, "nb_iter": args.nb_iter, "eot_samples": args.eot_samples,
-                                         "latent_iters": args.latent_iters, "latent_lr": args.latent_lr, "latent_c": args.latent_c},
+                                         "latent_iters": args.latent_iters, "latent_lr": args.latent_lr, "latent_c": args.latent_c,
+                                         "spsa_samples": args.spsa_samples, "spsa_delta": args.spsa_delta},
                           seed=args.seed, init_seed=args.init_seed, attack_ord=args.attack_ord)
     write_results(path, accuracies)
     return 0

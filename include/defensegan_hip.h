@@ -542,6 +542,33 @@ int dg_latent_attack(dg_handle* g, dg_clf* c, const float* x, const int32_t* lab
                      int32_t* best_row, float* out_z, float* out_margin, float* out_dist, float* out_dz, void* stream);
 
 /*
+ * The score-based black-box attack (no reference counterpart): SPSA with Rademacher directions and dg_bpda_step's projected sign
+ * step, L-infinity.  It reads only the attacked model's logits, so it works on the defended model, whose gradient is identically
+ * zero (defensegan_amd/csrc/dg_spsa.hip's header comment and DESIGN.md section 7, "SPSA", give the definition;
+ * network_builder.SPSA drives the two entries).  n direction pairs, probe size delta, iteration iter = k, image b of a call has
+ * the GLOBAL index g = first_image + b.  u_i[e] = +1 where bit (i & 31) of word (e & 3) of Philox4x32-10(key = (seed lo, seed hi),
+ * counter = (e >> 2, g, k ceil(n / 32) + (i >> 5), 0x53505341)) is set, else -1; never stored.  Device pointers; asynchronous on
+ * `stream`, on the current device; no host synchronisation, no graph capture, no atomics, no workspace; an image's result does not
+ * depend on which other images share the call.  DG_E_INVALID: a null required pointer, B < 1, n < 1, row_elems < 1 or above
+ * 2^31 - 1, more than 2^31 - 1 workgroups of 256 threads in one launch (B ceil(row_elems / 4) threads for the queries,
+ * B ceil(row_elems / 1024) workgroups for the step), classes < 2, delta <= 0, eps < 0, eps_iter < 0, clip_min > clip_max, iter < 0,
+ * first_image < 0, first_image + B > 2^32, iter ceil(n / 32) + ceil(n / 32) > 2^32, x_next == x_cur, out_grad equal to x_next,
+ * x_cur or x_orig.
+ */
+/* q [B, 2n + 1, row_elems]: q[b,0] = x_cur[b]; q[b,1+2i] = clip(x_cur[b] + delta u_i) and q[b,2+2i] = clip(x_cur[b] - delta u_i),
+ * clipped to [clip_min, clip_max].  float4 where row_elems is a multiple of 4 and the pointers are 16-byte aligned. */
+int dg_spsa_queries(const float* x_cur, int B, int64_t row_elems, int n, float delta, uint64_t seed, int64_t first_image, int iter,
+                    float clip_min, float clip_max, float* q, void* stream);
+/* logits [B (2n + 1), classes] of those queries as dg_clf_forward leaves them, labels [B] int32.  L = max_{j != y} Z_j - Z_y (0 for
+ * every query of an image whose label lies outside [0, classes)); dL_i = L(q+_i) - L(q-_i), formed in float64 and rounded once to
+ * float32, taken as 0 where that is not finite;  ghat[b,e] = float32(1 / (2 delta n)) * (the float32 sum over i, ascending, of
+ * dL_i u_i[e]);  x_next = clip(x_orig + clamp(x_cur + eps_iter * sign(ghat) - x_orig, -eps, eps), clip_min, clip_max), sign(0) = 0.
+ * out_grad [B, row_elems] (may be NULL; a buffer of its own) receives ghat. */
+int dg_spsa_step(const float* logits, const int32_t* labels, int B, int classes, int64_t row_elems, int n, float delta, uint64_t seed,
+                 int64_t first_image, int iter, const float* x_cur, const float* x_orig, float eps, float eps_iter, float clip_min,
+                 float clip_max, float* x_next, float* out_grad, void* stream);
+
+/*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
  * (no collective on the data path) and ONE all_gather assembles the evaluation message -- per rank `count` int32 words, e.g.
  * [n | labels (cap) | preds (cap) | diffs (cap, float32 bits)] as defensegan_amd/gan_defense.py:model_eval_gan_sharded builds it
