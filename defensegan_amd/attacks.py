@@ -1,6 +1,6 @@
 """The attacks on the classifier container of network_builder.py, where the reference takes them from ``cleverhans.attacks``:
 FastGradientMethod and CarliniWagnerL2 (the reference's own), ProjectedGradientDescent, and the three that see or get round the
-defense -- BPDA, SPSA, LatentAttack.  Every ``generate`` is the same host-side front end (the functions up to ``_pack``) around
+defense -- BPDA, SPSA, LatentAttack --, and DeepFool with the ``robustness`` it measures.  Every ``generate`` is the same host-side front end (the functions up to ``_pack``) around
 one or a few device calls; the arithmetic runs in the HIP library.  ``network_builder.X`` keeps resolving every name here."""
 from __future__ import annotations
 
@@ -740,3 +740,113 @@ class LatentAttack(object):
         info = {k: torch.cat([p[k] for p in parts]) for k in ("x_adv", "best_dist", "best_margin", "best_iter", "best_row", "z")}
         x_adv = info.pop("x_adv")
         return _pack(was_numpy, return_info, x_adv, info)
+
+
+# ---------------------------------------------------------------------- the minimal-perturbation attack: DeepFool
+_DEEPFOOL_REC_NOTE = (
+    "DeepFool on a model with the Defense-GAN reconstruction layer attached (add_rec_model) is not implemented, for CarliniWagnerL2's "
+    "reason: in the reference the gradient through ReconstructionLayer is identically zero (network_builder.py:266-271), so every "
+    "w_j is zero and no step exists; DeepFool through the projection would need BPDA.  Build the attack before add_rec_model, or "
+    "on a model without it.")
+DEEPFOOL_CALL_IMAGES = 1000                   # images per dg_deepfool call when batch_size is None: bounds the workspace, not the result
+
+
+class DeepFool(object):
+    """DeepFool (Moosavi-Dezfooli, Fawzi, Frossard 2016; cleverhans' ``DeepFool``), the minimal-L2 attack: no budget, no labels, one
+    asynchronous device call per ``batch_size`` images (``dg_deepfool``, defensegan_amd/csrc/dg_deepfool.hip; DESIGN.md section 7,
+    "DeepFool", gives the definition).  On the model's LOGITS, before any Softmax:
+
+        orig = first argmax at x;  cand[0 .. nb_candidate) = the classes of the largest logits at x, descending (fixed);  r = 0, adv = x
+        while the first argmax over all classes at adv is orig (at most max_iter times):
+            f_j = Z[cand_j] - Z[cand_0],  w_j = grad Z[cand_j] - grad Z[cand_0]  at adv;   pert_j = (|f_j| + 1e-5) / ||w_j||_2
+            j* = the first index of the smallest pert_j;   r += pert_j* w_j* / ||w_j*||_2;   adv = clip(x + r, clip_min, clip_max)
+        x_adv = clip(x + (1 + overshoot) r, clip_min, clip_max)
+
+    ``||w_j|| == 0`` gives ``pert_j = +inf``, which is never chosen; an image with nothing to choose stops and keeps its r.  An image
+    whose logits hold a NaN stops and returns ``clip(x + (1 + overshoot) r)`` from the last finite state.
+
+    ``generate`` returns ``x_adv`` (NumPy in gives NumPy out; a device tensor in gives a device tensor out on the caller's current
+    stream); ``return_info=True`` adds ``(r_norm, iters, final_class)``: ``||x_adv - x||_2`` [n] float32, the iterations the image
+    was active and the first argmax at ``x_adv`` [n] int32.  ``batch_size`` only bounds the images per device call (default
+    DEEPFOOL_CALL_IMAGES): every reduction is per image and in a fixed order, so the result does not depend on it, bit for bit.
+    ``sess`` / ``back`` are accepted for signature compatibility and ignored.
+
+    A model with the reconstruction layer attached raises NotImplementedError (see _DEEPFOOL_REC_NOTE); an unknown keyword is a
+    ValueError."""
+
+    DEFAULTS = dict(nb_candidate=10, overshoot=0.02, max_iter=50, clip_min=0.0, clip_max=1.0, batch_size=None, return_info=False)
+
+    def __init__(self, model: MLP, back="tf", sess=None):
+        self.model = model
+
+    @classmethod
+    def parse_params(cls, params):
+        """DEFAULTS overlaid with ``params``, checked on the host: what ``generate`` and ``robustness`` accept."""
+        unknown = set(params) - set(cls.DEFAULTS)
+        if unknown:
+            raise ValueError("unknown DeepFool parameters: %s" % sorted(unknown))
+        p = dict(cls.DEFAULTS, **params)
+        if int(p["nb_candidate"]) < 2:
+            raise ValueError("nb_candidate must be >= 2, got %d" % int(p["nb_candidate"]))
+        if int(p["max_iter"]) < 0:
+            raise ValueError("max_iter must be >= 0, got %d" % int(p["max_iter"]))
+        _check_iterative(batch_size=p["batch_size"])
+        p["clip_min"], p["clip_max"] = _clip_bounds(p["clip_min"], p["clip_max"])
+        return p
+
+    def generate(self, x, **params):
+        import torch
+        p = self.parse_params(params)
+        m = self.model
+        if m.rec_layer is not None:
+            raise NotImplementedError(_DEEPFOOL_REC_NOTE)
+        dev = nb._ready(m)
+        if int(p["nb_candidate"]) > m.nb_classes:
+            raise ValueError("nb_candidate must not exceed the model's %d classes, got %d" % (m.nb_classes, int(p["nb_candidate"])))
+        t, was_numpy = nb._images(m, x, dev, batch="n", nonempty=True)
+        n = int(t.shape[0])
+        x_adv = torch.empty_like(t)
+        r_norm = torch.empty(n, dtype=torch.float32, device=dev)
+        iters = torch.empty(n, dtype=torch.int32, device=dev)
+        final_class = torch.empty(n, dtype=torch.int32, device=dev)
+        info = bool(p["return_info"])
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            for a, b in _chunks(n, p["batch_size"] or DEEPFOOL_CALL_IMAGES):
+                _native.check(_native.load().dg_deepfool(
+                    m._handle, t[a:b].data_ptr(), b - a, int(p["nb_candidate"]), float(p["overshoot"]), int(p["max_iter"]), p["clip_min"],
+                    p["clip_max"], x_adv[a:b].data_ptr(), r_norm[a:b].data_ptr() if info else None, iters[a:b].data_ptr() if info else None,
+                    final_class[a:b].data_ptr() if info else None, stream))
+        return _pack(was_numpy, info, x_adv, r_norm, iters, final_class)
+
+
+def robustness(model: MLP, x, **deepfool_params):
+    """The DeepFool robustness of ``model`` on the images ``x`` (Moosavi-Dezfooli et al. 2016, eq. 15), a dict of floats:
+
+        rho         the mean of ||x_adv - x||_2 / ||x||_2 over the images with ||x||_2 > 0
+        mean_l2     the mean of ||x_adv - x||_2
+        fooled      the share of images whose first argmax at x_adv is not the one at x
+        mean_iters  the mean number of iterations an image was active
+
+    ``deepfool_params``: ``DeepFool.generate``'s, without return_info.  Norms on the device (``dg_deepfool``'s r_norm, ``dg_row_norms``),
+    means in float64 on the host; a NaN image makes rho and mean_l2 NaN."""
+    import torch
+    if "return_info" in deepfool_params:
+        raise ValueError("robustness: return_info is not a parameter here")
+    DeepFool.parse_params(deepfool_params)                        # refusals before the device is touched
+    if model.rec_layer is not None:
+        raise NotImplementedError(_DEEPFOOL_REC_NOTE)
+    dev = nb._ready(model)
+    t, _ = nb._images(model, x, dev, batch="n", nonempty=True)
+    _, r_norm, iters, final_class = DeepFool(model).generate(t, return_info=True, **deepfool_params)
+    orig = torch.cat([model.eval_batch(t[a:b], None, None, sync=False)[1] for a, b in _chunks(int(t.shape[0]), DEEPFOOL_CALL_IMAGES)])
+    return robustness_summary(r_norm.cpu().numpy(), _row_norms(t, None, 2).cpu().numpy(), iters.cpu().numpy(), final_class.cpu().numpy(),
+                              orig.cpu().numpy())
+
+
+def robustness_summary(r_norm, x_norm, iters, final_class, orig):
+    """``robustness``'s dict from its per-image arrays (host, float64 means)."""
+    r, xn = np.asarray(r_norm, np.float64), np.asarray(x_norm, np.float64)
+    nz = xn > 0
+    return {"rho": float((r[nz] / xn[nz]).mean()) if nz.any() else float("nan"), "mean_l2": float(r.mean()),
+            "fooled": float((np.asarray(final_class) != np.asarray(orig)).mean()), "mean_iters": float(np.asarray(iters, np.float64).mean())}

@@ -400,6 +400,7 @@ int dg_clf_destroy(dg_clf* h) {
     bpda_release(h->bpda);
     pgd_release(h->pgd);
     critic_release(h->critic);
+    deepfool_release(h->deepfool);
     delete h;
     return DG_OK;
 }

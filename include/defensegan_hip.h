@@ -569,6 +569,35 @@ int dg_spsa_step(const float* logits, const int32_t* labels, int B, int classes,
                  float clip_max, float* x_next, float* out_grad, void* stream);
 
 /*
+ * DeepFool (Moosavi-Dezfooli et al. 2016; no reference counterpart: cleverhans is an empty submodule there): the minimal L2
+ * perturbation over the nearest linearised decision boundary, the whole loop enqueued by this one call
+ * (defensegan_amd/csrc/dg_deepfool.hip's header comment and DESIGN.md section 7, "DeepFool", give the definition; attacks.DeepFool).
+ * x [B,H,W,C]; no labels; the LOGITS are read, before any Softmax.  orig = the first arg-max at x; the nb_candidate classes of the
+ * largest logits at x, descending, ties to the lower class, are fixed for the run; r = 0, adv = x.  While the first arg-max over
+ * all classes at adv is orig the image is active, and an iteration does, with f_j and w_j the differences of logit and class
+ * gradient between candidate j and candidate 0 at adv:  pert_j = (|f_j| + 1e-5) / ||w_j||_2,  j* = the first index of the minimum,
+ * r += pert_j* w_j* / ||w_j*||_2,  adv = clip(x + r, clip_min, clip_max).  After max_iter iterations, or when no image is active:
+ *   x_adv       [B,H,W,C] clip(x + (1 + overshoot) r, clip_min, clip_max) (required; may be x)
+ *   r_norm      [B] ||x_adv - x||_2 of what was written                                       (may be NULL)
+ *   iters       [B] int32, the iterations the image entered active                            (may be NULL)
+ *   final_class [B] int32, the first arg-max at x_adv (one more forward); a NaN is never a candidate, class 0 where class 0 is a NaN
+ *               or nothing else is left                                                       (may be NULL)
+ * ||w_j|| == 0 gives pert_j = +inf; +inf and NaN are never the minimum; an image without a minimum becomes inactive and keeps its r.
+ * An image whose logits hold a NaN, at x or after a step, becomes inactive and that step is taken back: it returns
+ * clip(x + (1 + overshoot) r) from the last finite state.  DG_E_INVALID: null h, x or x_adv, B < 1, nb_candidate < 2 or above the
+ * number of logits (or above 2048), max_iter < 0, clip_min > clip_max, B * nb_candidate or B * max_iter above 2^31 - 1; DG_E_STATE:
+ * incomplete weights.  Device pointers; asynchronous on `stream` except that every second iteration the count of active images is
+ * read back and the loop ends when it is zero, which changes no bit of the result; no graph capture, no float atomics, every sum in
+ * a fixed order: a call repeated returns the same bits and an image's result does not depend on which other images share the
+ * call.  The workspace grows on demand (nb_candidate rows per image through the classifier).
+ */
+int dg_deepfool(dg_clf* h, const float* x, int B, int nb_candidate, float overshoot, int max_iter, float clip_min, float clip_max,
+                float* x_adv, float* r_norm, int32_t* iters, int32_t* final_class, void* stream);
+/* choices [max_iter, B] int32 (device): the j* of every step of the handle's LAST dg_deepfool call, -1 where the image took none
+ * (inactive, no minimum, or an iteration the early exit skipped); DG_E_STATE unless that call had this B and max_iter (>= 1). */
+int dg_deepfool_choices(dg_clf* h, int B, int max_iter, int32_t* choices, void* stream);
+
+/*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
  * (no collective on the data path) and ONE all_gather assembles the evaluation message -- per rank `count` int32 words, e.g.
  * [n | labels (cap) | preds (cap) | diffs (cap, float32 bits)] as defensegan_amd/gan_defense.py:model_eval_gan_sharded builds it
