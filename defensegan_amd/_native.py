@@ -86,6 +86,7 @@ SYMBOLS = [
     ("dg_spsa_step", _i, [_vp, _vp, _i, _i, _i64, _i, _f, _u64, _i64, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp]),
     ("dg_deepfool", _i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     ("dg_deepfool_choices", _i, [_vp, _i, _i, _vp, _vp]),
+    ("dg_ead", _i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _f, _i, _i, _i, C.c_double, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

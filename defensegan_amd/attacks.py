@@ -1,5 +1,5 @@
 """The attacks on the classifier container of network_builder.py, where the reference takes them from ``cleverhans.attacks``:
-FastGradientMethod and CarliniWagnerL2 (the reference's own), ProjectedGradientDescent, and the three that see or get round the
+FastGradientMethod and CarliniWagnerL2 (the reference's own), ElasticNetMethod (the L1 attack), ProjectedGradientDescent, and the three that see or get round the
 defense -- BPDA, SPSA, LatentAttack --, and DeepFool with the ``robustness`` it measures.  Every ``generate`` is the same host-side front end (the functions up to ``_pack``) around
 one or a few device calls; the arithmetic runs in the HIP library.  ``network_builder.X`` keeps resolving every name here."""
 from __future__ import annotations
@@ -233,6 +233,91 @@ class CarliniWagnerL2(object):
                 best_l2.data_ptr(), best_class.data_ptr(), final_const.data_ptr() if return_search else None,
                 chunk_stop.data_ptr() if return_search else None, stream))
         return _pack(was_numpy, return_info, out, best_l2, best_class, *((final_const, chunk_stop) if return_search else ()))
+
+
+EAD_RULES = {"EN": 0, "L1": 1}                # dg_ead's decision_rule
+
+
+class ElasticNetMethod(object):
+    """The elastic-net attack (Chen et al. 2018, EAD; cleverhans' ``ElasticNetMethod``), the suite's L1 attack: Carlini-Wagner's loss
+    plus ``beta * ||x_adv - clip(x)||_1``, minimised by iterative shrinkage-thresholding (``fista``: with the FISTA extrapolation) at
+    the rate ``learning_rate * sqrt(1 - i / max_iterations)``, restated and run as ONE asynchronous device call (``dg_ead``; the
+    algorithm is in defensegan_amd/csrc/dg_ead.hip's header comment and DESIGN.md section 7, "Elastic net").  It needs no L1
+    projection, so no sort.  ``sess`` / ``back`` are accepted for signature compatibility and ignored.
+
+    ``generate(x, y=None, y_target=None, **params)`` has ``CarliniWagnerL2.generate``'s conventions: NumPy in gives NumPy out, a torch
+    tensor in gives a tensor out (on the caller's current stream, not waited for); ``y`` / ``y_target`` one-hot or class indices;
+    without either the label is the model's own first argmax on ``x``.  ``decision_rule`` ranks the successful iterates: "EN" by
+    ``||d||_2^2 + beta ||d||_1``, "L1" by ``||d||_1``, d = iterate - clip(x).  ``return_info=True`` also returns ``(best_dist,
+    best_class)``: the rule's criterion at ``x_adv`` and its class (1e10 / -1 where no iterate succeeded; ``x_adv`` is then clip(x)
+    bit for bit); ``return_search=True`` then also ``(final_const [B] float64, chunk_stop [binary_search_steps, chunks] int32)`` as
+    CarliniWagnerL2's.  ``nb_classes`` and ``feed`` are accepted and ignored.  As for CarliniWagnerL2, ``abort_early`` changes which
+    iterations count, not how long the call takes.
+
+    The defaults are those of cleverhans' ``ElasticNetMethod`` as remembered (batch_size=1, confidence=0, beta=1e-3,
+    decision_rule="EN", fista=True, learning_rate=1e-2, binary_search_steps=9, max_iterations=1000, abort_early=False,
+    initial_const=1e-3, clip_min=0, clip_max=1): nothing in the reference pins them (cleverhans is an empty, un-pinned submodule).
+
+    ``decision_rule`` outside {"EN", "L1"} and ``beta < 0`` are a ValueError before any device work; an unknown keyword is a
+    TypeError.  A model with the reconstruction layer attached raises NotImplementedError, for _CW_REC_NOTE's reason: the
+    reference's gradient through ReconstructionLayer is identically zero."""
+
+    DEFAULTS = dict(batch_size=1, confidence=0.0, beta=1e-3, decision_rule="EN", fista=True, learning_rate=1e-2, binary_search_steps=9,
+                    max_iterations=1000, abort_early=False, initial_const=1e-3, clip_min=0.0, clip_max=1.0)
+
+    def __init__(self, model: MLP, back="tf", sess=None):
+        self.model = model
+
+    @classmethod
+    def parse_params(cls, params):
+        """DEFAULTS overlaid with ``params``, checked on the host; ``decision_rule`` comes back as dg_ead's integer."""
+        unknown = set(params) - set(cls.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown ElasticNetMethod parameters: %s" % sorted(unknown))
+        p = dict(cls.DEFAULTS, **params)
+        if p["decision_rule"] not in EAD_RULES:
+            raise ValueError("decision_rule must be 'EN' or 'L1', got %r" % (p["decision_rule"],))
+        if not float(p["beta"]) >= 0:
+            raise ValueError("beta must be >= 0, got %r" % (p["beta"],))
+        if int(p["max_iterations"]) < 1:
+            raise ValueError("max_iterations must be >= 1, got %d" % int(p["max_iterations"]))
+        if int(p["batch_size"]) < 1:
+            raise ValueError("batch_size must be >= 1")
+        if not float(p["clip_min"]) < float(p["clip_max"]):
+            raise ValueError("clip_min must be below clip_max")
+        p["decision_rule"] = EAD_RULES[p["decision_rule"]]
+        return p
+
+    def generate(self, x, y=None, y_target=None, return_info=False, return_search=False, nb_classes=None, feed=None, **params):
+        import torch
+        p = self.parse_params(params)
+        m = self.model
+        if m.rec_layer is not None:
+            raise NotImplementedError("ElasticNetMethod: " + _CW_REC_NOTE)
+        if y is not None and y_target is not None:
+            raise ValueError("give y or y_target, not both")
+        dev = nb._ready(m)
+        t, was_numpy = nb._images(m, x, dev, batch="B")
+        B = int(t.shape[0])
+        if B == 0:
+            raise ValueError("x holds no images")
+        targeted = y_target is not None
+        lab = _labels(y_target if targeted else y, B, dev, required=False, range_words="cw", nb_classes=m.nb_classes)
+        out = torch.empty_like(t)
+        best_dist = torch.empty(B, dtype=torch.float32, device=dev)
+        best_class = torch.empty(B, dtype=torch.int32, device=dev)
+        nsteps, chunks = max(int(p["binary_search_steps"]), 0), -(-B // int(p["batch_size"]))
+        final_const = torch.empty(B, dtype=torch.float64, device=dev)
+        chunk_stop = torch.empty(nsteps, chunks, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _native.check(_native.load().dg_ead(
+                m._handle, t.data_ptr(), _ptr(lab), B, 1 if targeted else 0, int(p["batch_size"]), float(p["confidence"]), float(p["beta"]),
+                p["decision_rule"], 1 if p["fista"] else 0, float(p["learning_rate"]), int(p["binary_search_steps"]),
+                int(p["max_iterations"]), 1 if p["abort_early"] else 0, float(p["initial_const"]), float(p["clip_min"]), float(p["clip_max"]),
+                out.data_ptr(), best_dist.data_ptr(), best_class.data_ptr(), final_const.data_ptr() if return_search else None,
+                chunk_stop.data_ptr() if return_search else None, stream))
+        return _pack(was_numpy, return_info, out, best_dist, best_class, *((final_const, chunk_stop) if return_search else ()))
 
 
 # ---------------------------------------------------------------------- the attack that sees the defense: BPDA / EOT

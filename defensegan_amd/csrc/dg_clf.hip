@@ -401,6 +401,7 @@ int dg_clf_destroy(dg_clf* h) {
     pgd_release(h->pgd);
     critic_release(h->critic);
     deepfool_release(h->deepfool);
+    ead_release(h->ead);
     delete h;
     return DG_OK;
 }

@@ -1,4 +1,4 @@
-// The classifier handle as its source files see it (dg_deepfool.hip, the DeepFool loop, besides those named here): dg_clf.hip (the layers, the evaluation and input-gradient kernels),
+// The classifier handle as its source files see it (dg_deepfool.hip, the DeepFool loop, and dg_ead.hip, the elastic-net attack, besides those named here): dg_clf.hip (the layers, the evaluation and input-gradient kernels),
 // dg_cw.hip (the Carlini-Wagner attack), dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation), dg_bpda.hip (the BPDA/EOT step), dg_pgd.hip (PGD on the bare
 // classifier), dg_ball.hip (the per-image norms and steps of the L1 / L2 attacks) and dg_critic.hip (the WGAN-GP critic's cost, gradient and step).  Everything here is internal to the library: plain C++
 // under hidden visibility, nothing of it is exported.
@@ -40,6 +40,7 @@ struct BpdaWork;     // dg_bpda.hip
 struct PgdWork;      // dg_pgd.hip
 struct CriticWork;   // dg_critic.hip
 struct DeepfoolWork; // dg_deepfool.hip
+struct EadWork;      // dg_ead.hip
 
 struct dg_clf {
     int device = 0;
@@ -67,6 +68,7 @@ struct dg_clf {
     PgdWork* pgd = nullptr;                   // PGD's seed and its two iterate buffers, grown on demand
     CriticWork* critic = nullptr;             // the WGAN-GP critic's three-batch workspace, grown on demand
     DeepfoolWork* deepfool = nullptr;         // DeepFool's candidates, seeds, iterate rows and per-image state, grown on demand
+    EadWork* ead = nullptr;                   // the elastic-net attack's slack / iterate rows and per-image state, grown on demand
 
     int pixels() const { return in_h * in_w * in_c; }
 };
@@ -119,6 +121,7 @@ void bpda_release(BpdaWork* w);      // dg_bpda.hip
 void pgd_release(PgdWork* w);        // dg_pgd.hip
 void critic_release(CriticWork* w);  // dg_critic.hip
 void deepfool_release(DeepfoolWork* w);   // dg_deepfool.hip
+void ead_release(EadWork* w);        // dg_ead.hip
 
 // ---- dg_clf_train.hip -------------------------------------------------------------------------------------------------------------
 // How a Conv2D / Linear layer's weight gradient over B images is cut: `slots` runs of kc terms of its reduction axis, each slot

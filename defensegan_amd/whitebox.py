@@ -14,6 +14,7 @@ device:
         --defense_type defense_gan --attack_type latent --latent_iters 100 --rec_rr 10
     python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --init_path output/gans/mnist \\
         --defense_type defense_gan --attack_type spsa --spsa_samples 32 --spsa_delta 0.01 --num_tests 100
+    python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --defense_type none --attack_type ead --ead_beta 1e-2 --ead_rule L1
 
 Kept from the reference: ``RandomState([11, 24, 1990])`` for the training schedule; the clean accuracy on the (reconstructed) test
 split printed after every epoch; with ``defense_gan`` the reconstruction layer is attached AFTER training and BEFORE the attack
@@ -29,9 +30,12 @@ import numpy as np
 from . import config, datasets, gan_defense, network_builder, py2pickle, utils_tf
 from .blackbox import SEED, _Phase, _accuracy, _labels, load_recs, result_path
 
-ATTACKS = ("fgsm", "cw", "pgd", "bpda", "latent", "spsa")
+ATTACKS = ("fgsm", "cw", "pgd", "bpda", "latent", "spsa", "ead")
 # whitebox.py:203-209; 'feed' is TensorFlow's business
 CW_PARAMS = {"binary_search_steps": 1, "max_iterations": 100, "learning_rate": 10.0, "initial_const": 100}
+# the elastic-net attack (network_builder.ElasticNetMethod): this setting is chosen here, not taken from the reference, which has no ead
+EAD_PARAMS = {"binary_search_steps": 5, "max_iterations": 100, "learning_rate": 1e-2, "initial_const": 1.0}
+EAD_DEFAULTS = {"ead_beta": 1e-3, "ead_rule": "EN"}
 ITERATIVE_DEFAULTS = {"eps_iter": 0.05, "nb_iter": 10, "eot_samples": 1}
 # the latent-space attack (network_builder.LatentAttack): Adam steps on z, their learning rate, the weight of the classification term
 LATENT_DEFAULTS = {"latent_iters": 100, "latent_lr": 0.05, "latent_c": 1.0}
@@ -50,29 +54,35 @@ def attack_kind(attack_type):
     if "fgsm" in t:
         return "fgsm", rand
     base = t.replace("rand", "").strip("_+")
-    if base in ATTACKS and not (rand and base in ("cw", "latent", "spsa")):
+    if base in ATTACKS and not (rand and base in ("cw", "latent", "spsa", "ead")):
         return base, rand
-    raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, pgd (defense_type none / adv_tr), bpda or latent (defense_gan), spsa" % (attack_type,))
+    raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, ead, pgd (defense_type none / adv_tr), bpda or latent (defense_gan), spsa" % (attack_type,))
 
 
 def attack_ord_value(attack_ord, kind=None):
     """``attack_ord`` (np.inf, 1, 2 or their names 'inf', '1', '2') as np.inf or an int, checked against the attack ``kind``: fgsm
     takes 1 and 2 (``FastGradientMethod``'s ord), pgd and bpda take 2 (1 is NotImplementedError: the L1 projection needs a sort), cw
-    is an L2 attack already and takes none, as do latent and spsa."""
+    is an L2 attack already and takes none, as do latent and spsa; ead is the L1 attack and takes none either."""
     who = "attack_ord" if kind is None else "attack_ord with attack_type %s" % kind
-    allowed = {"fgsm": (np.inf, 1, 2), "pgd": (np.inf, 2), "bpda": (np.inf, 2), "cw": (np.inf,), "latent": (np.inf,), "spsa": (np.inf,)}.get(kind, (np.inf, 1, 2))
+    allowed = {"fgsm": (np.inf, 1, 2), "pgd": (np.inf, 2), "bpda": (np.inf, 2), "cw": (np.inf,), "ead": (np.inf,), "latent": (np.inf,), "spsa": (np.inf,)}.get(kind, (np.inf, 1, 2))
     return network_builder._attack_ord(attack_ord, allowed, who)
 
 
 def _attack_params(kind, attack_params):
     """The overrides ``attack_params`` holds for this attack: eps_iter / nb_iter (pgd, bpda), eot_samples (bpda), any
-    CarliniWagnerL2 parameter (cw), latent_iters / latent_lr / latent_c (latent), eps_iter / nb_iter / spsa_samples / spsa_delta (spsa).  Values of None and the iterative attacks' keys given to another attack are left out."""
+    CarliniWagnerL2 parameter (cw), latent_iters / latent_lr / latent_c (latent), eps_iter / nb_iter / spsa_samples / spsa_delta (spsa), ead_beta / ead_rule and any ElasticNetMethod parameter (ead).  Values of None and the iterative attacks' keys given to another attack are left out."""
     given = {k: v for k, v in (attack_params or {}).items() if v is not None}
-    known = set(ITERATIVE_DEFAULTS) | set(network_builder.CarliniWagnerL2.DEFAULTS) | set(LATENT_DEFAULTS) | set(SPSA_DEFAULTS)
+    known = (set(ITERATIVE_DEFAULTS) | set(network_builder.CarliniWagnerL2.DEFAULTS) | set(LATENT_DEFAULTS) | set(SPSA_DEFAULTS)
+             | set(EAD_DEFAULTS) | set(network_builder.ElasticNetMethod.DEFAULTS))
     if set(given) - known:
         raise ValueError("unknown attack_params: %s" % sorted(set(given) - known))
     if kind == "cw":
         return {k: v for k, v in given.items() if k in network_builder.CarliniWagnerL2.DEFAULTS}
+    if kind == "ead":
+        out = {k: v for k, v in given.items() if k in network_builder.ElasticNetMethod.DEFAULTS}
+        out.setdefault("beta", given.get("ead_beta", EAD_DEFAULTS["ead_beta"]))
+        out.setdefault("decision_rule", given.get("ead_rule", EAD_DEFAULTS["ead_rule"]))
+        return out
     if kind == "latent":
         return {k: given.get(k, d) for k, d in LATENT_DEFAULTS.items()}
     keys = {"pgd": ("eps_iter", "nb_iter"), "bpda": ("eps_iter", "nb_iter", "eot_samples"), "spsa": ("eps_iter", "nb_iter")}.get(kind, ())
@@ -85,7 +95,7 @@ def _attack_params(kind, attack_params):
 def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate=0.001, nb_epochs=10, eps=0.3, alpha=0.05,
              online_training=False, train_on_recs=False, test_on_dev=True, attack_type="fgsm", defense_type="none", num_tests=-1,
              num_train=-1, fgsm_eps_tr=0.15, same_init=False, recs=None, attack_params=None, seed=SEED, init_seed=0, phases=None,
-             attack_ord=np.inf):
+             attack_ord=np.inf, norms=None):
     """whitebox.py:56-233.  ``gan``: a DefenseGANBase with its generator loaded, or None (``defense_type`` 'none' and 'adv_tr' need
     none); ``model``: the classifier's MLP (initialised with the reference's initialisers from ``init_seed`` when its weights are not
     set); ``data`` = (train_images, train_labels, test_images, test_labels), the ORIGINAL images in generator range, labels one-hot
@@ -101,6 +111,10 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
     from the training ``RandomState``):
       fgsm, rand_fgsm   FastGradientMethod, the label the model's own prediction (whitebox.py:198-200)
       cw                CarliniWagnerL2 with binary_search_steps 1, max_iterations 100, learning_rate 10, initial_const 100
+      ead               ElasticNetMethod (the L1 attack) with EAD_PARAMS: binary_search_steps 5, max_iterations 100, learning_rate
+                        0.01, initial_const 1 -- chosen here, the reference has no ead; ``attack_params`` ead_beta (1e-3), ead_rule
+                        ('EN') and any ElasticNetMethod parameter.  ``norms``: a dict that receives 'l1' and 'l2', the means of
+                        ||x_adv - x||_1 and ||x_adv - x||_2 over the images the attack succeeded on (NaN when on none), and 'successes'
       pgd               ProjectedGradientDescent on the true labels: 'none' and 'adv_tr' only
       bpda              BPDA on the true labels: 'defense_gan' only
       latent            LatentAttack on the true labels, ``gan.rec_rr`` restarts per image: 'defense_gan' only.  x_adv = G(z) lies in
@@ -111,7 +125,7 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
     ``attack_params`` overrides ``eps_iter`` (0.05), ``nb_iter`` (10), ``eot_samples`` (1) of pgd / bpda and any CarliniWagnerL2
     parameter.  pgd with 'defense_gan' or bpda without it is a ValueError.  ``attack_ord`` (default np.inf): 2 runs pgd / bpda in an
     L2 ball of radius ``eps`` (their ``ord``), 1 or 2 runs fgsm / rand_fgsm as FGM with that norm; 1 with pgd / bpda is
-    NotImplementedError, any value but np.inf with cw a ValueError.
+    NotImplementedError, any value but np.inf with cw or ead a ValueError.
 
     ``defense_gan``: the reconstruction layer is attached after training (``same_init``: with one sigma = 1 draw of
     [batch_size * rec_rr, latent_dim] as every batch's z0), the attack is built on that model, and the accuracy comes from
@@ -119,7 +133,8 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
     zero gradient and returns clip(x), as in the reference.  DEVIATION for cw: the reference builds CarliniWagnerL2 on the defended
     model as well, where the zero gradient reduces it to the tanh round trip of x at a hundred defended evaluations per batch;
     ``CarliniWagnerL2`` refuses such a model here, so the attack is built BEFORE ``add_rec_model``, sees the bare classifier, and its
-    images are then evaluated through the projection (one printed line says so).
+    images are then evaluated through the projection (one printed line says so).  ead behaves as cw does: ``ElasticNetMethod`` refuses a
+    defended model for the same reason, is built before ``add_rec_model``, and the same notice is printed.
 
     Returns ``(accuracy on the adversarial images, 0, roc_info or None)``.  ``test_on_dev`` and ``rec_data_path`` are the data
     loader's business and are accepted for signature compatibility.  ``phases``: a dict that receives the seconds spent in
@@ -188,9 +203,9 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
     kind, rand = kind
 
     attack = None
-    if kind == "cw" and defended:
-        attack = network_builder.CarliniWagnerL2(model)
-        print("[*] cw with defense_gan: the attack is built before the reconstruction layer is attached and sees the BARE classifier "
+    if kind in ("cw", "ead") and defended:
+        attack = (network_builder.CarliniWagnerL2 if kind == "cw" else network_builder.ElasticNetMethod)(model)
+        print("[*] " + kind + " with defense_gan: the attack is built before the reconstruction layer is attached and sees the BARE classifier "
               "(the reference's sees a zero gradient); its images are evaluated through the projection")
     z_init = None
     if defended:
@@ -210,6 +225,11 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
         elif kind == "cw":
             attack = attack or network_builder.CarliniWagnerL2(model)
             x_adv = attack.generate(test_adv_from, **dict(CW_PARAMS, batch_size=batch_size, **extra))
+        elif kind == "ead":
+            attack = attack or network_builder.ElasticNetMethod(model)
+            x_adv, _, ead_class = attack.generate(test_adv_from, return_info=True, **dict(EAD_PARAMS, batch_size=batch_size, **extra))
+            if norms is not None:
+                norms.update(ead_norms(x_adv, test_adv_from, ead_class, dev))
         elif kind == "pgd":
             attack = network_builder.ProjectedGradientDescent(model)
             x_adv = attack.generate(test_adv_from, test_labels, eps=eps, clip_min=min_val, clip_max=1.0, seed=seed,
@@ -237,6 +257,18 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
     acc_adv = correct / float(max(n, 1))
     print("Test accuracy on adversarial examples: %0.4f\n" % acc_adv)
     return acc_adv, 0, roc_info
+
+
+def ead_norms(x_adv, x, best_class, dev):
+    """{'l1', 'l2', 'successes'}: the means of the per-image ||x_adv - x||_1 and ||x_adv - x||_2 (``dg_row_norms``; ord = 1 there is a
+    plain sum, not a projection) over the images with ``best_class != -1``, float64 means on the host; NaN when none succeeded."""
+    a, b = network_builder._to_device(np.asarray(x_adv, np.float32), dev), network_builder._to_device(np.asarray(x, np.float32), dev)
+    ok = np.asarray(best_class) != -1
+    out = {"successes": int(ok.sum())}
+    for name, o in (("l1", 1), ("l2", 2)):
+        v = network_builder._row_norms(a, b, o).cpu().numpy().astype(np.float64)
+        out[name] = float(v[ok].mean()) if ok.any() else float("nan")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------- result files, CLI
@@ -267,12 +299,14 @@ def get_results_dir_filename(flags, gan):
     return results_dir, result_file_name
 
 
-def write_results(path, accuracies):
+def write_results(path, accuracies, norms=None):
     """whitebox.py:295-306: the line ``str(acc) + ' ' + '0 '`` (appended) and, with roc_info, ``*_roc.pkl`` in a pickle the
-    Python-2 reference reads."""
+    Python-2 reference reads.  ``norms`` (ead: whitebox()'s dict) adds two entries to the line: ``l1=<mean> l2=<mean>``."""
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with open(path, "a") as f:
         f.writelines([str(accuracies[i]) + " " for i in range(2)])
+        if norms:
+            f.write("l1=%s l2=%s " % (norms["l1"], norms["l2"]))
         f.write("\n")
     print("[*] saved accuracy in {}".format(path))
     if accuracies[2]:
@@ -299,7 +333,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--random_test_iter", type=int, default=-1, help="accepted and ignored, as in the reference")
     ap.add_argument("--online_training", action="store_true", help="not implemented (NotImplementedError)")
     ap.add_argument("--defense_type", default="none", choices=["none", "defense_gan", "adv_tr"], help="Type of defense")
-    ap.add_argument("--attack_type", default="none", help="Type of attack [fgsm|cw|rand_fgsm|pgd|bpda|latent|spsa]; none: train and stop")
+    ap.add_argument("--attack_type", default="none", help="Type of attack [fgsm|cw|ead|rand_fgsm|pgd|bpda|latent|spsa]; none: train and stop")
     ap.add_argument("--results_dir", default=None, help="The final subdirectory of the results.")
     ap.add_argument("--model", default="F", choices=sorted(network_builder.MODELS), help="The classifier model.")
     ap.add_argument("--debug_dir", default="temp", help="accepted and ignored (the reference's qualitative debug output)")
@@ -314,6 +348,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--latent_iters", type=int, default=None, help="latent: Adam steps on z (default 100); --rec_rr is its restarts per image")
     ap.add_argument("--latent_lr", type=float, default=None, help="latent: Adam's learning rate (default 0.05)")
     ap.add_argument("--latent_c", type=float, default=None, help="latent: weight of the classification term (default 1)")
+    ap.add_argument("--ead_beta", type=float, default=EAD_DEFAULTS["ead_beta"], help="ead: weight of the L1 term (default 1e-3)")
+    ap.add_argument("--ead_rule", default=EAD_DEFAULTS["ead_rule"], choices=["EN", "L1"],
+                    help="ead: the best iterate is the successful one of the smallest elastic-net (EN) or L1 distance (default EN)")
     ap.add_argument("--attack_ord", default="inf", choices=["inf", "1", "2"],
                     help="norm of the attack's ball: pgd / bpda take inf or 2, fgsm / rand_fgsm inf, 1 or 2 (default inf)")
     ap.add_argument("--seed", type=int, default=SEED, help="seed of the Dropout masks and the latent draws")
@@ -356,6 +393,7 @@ def main(argv=None) -> int:
     model = network_builder.MODELS[args.model](input_shape=(None,) + tuple(x_tr.shape[1:]), nb_classes=args.nb_classes)
     results_dir, name = get_results_dir_filename(args, gan)
     path = result_path(results_dir, name, args.results_dir)
+    norms = {}
     accuracies = whitebox(gan, model, (x_tr, y_tr, x_te, y_te), rec_data_path=args.rec_path, batch_size=batch_size,
                           learning_rate=args.learning_rate, nb_epochs=args.nb_epochs, eps=args.fgsm_eps, alpha=args.alpha,
                           online_training=args.online_training, train_on_recs=args.train_on_recs, attack_type=args.attack_type,
@@ -363,9 +401,10 @@ def main(argv=None) -> int:
                           fgsm_eps_tr=args.fgsm_eps_tr, same_init=args.same_init, recs=recs,
                           attack_params={"eps_iter": args.eps_iter, "nb_iter": args.nb_iter, "eot_samples": args.eot_samples,
                                          "latent_iters": args.latent_iters, "latent_lr": args.latent_lr, "latent_c": args.latent_c,
-                                         "spsa_samples": args.spsa_samples, "spsa_delta": args.spsa_delta},
-                          seed=args.seed, init_seed=args.init_seed, attack_ord=args.attack_ord)
-    write_results(path, accuracies)
+                                         "spsa_samples": args.spsa_samples, "spsa_delta": args.spsa_delta,
+                                         "ead_beta": args.ead_beta, "ead_rule": args.ead_rule},
+                          seed=args.seed, init_seed=args.init_seed, attack_ord=args.attack_ord, norms=norms)
+    write_results(path, accuracies, norms)
     return 0
 
 

@@ -598,6 +598,28 @@ int dg_deepfool(dg_clf* h, const float* x, int B, int nb_candidate, float oversh
 int dg_deepfool_choices(dg_clf* h, int B, int max_iter, int32_t* choices, void* stream);
 
 /*
+ * The elastic-net attack (Chen et al. 2018, EAD; cleverhans' ElasticNetMethod; no reference counterpart): Carlini-Wagner's loss plus
+ * beta * ||x_adv - x0||_1, minimised by iterative shrinkage-thresholding, with `fista` by FISTA; the L1 attack of the suite
+ * (defensegan_amd/csrc/dg_ead.hip's header comment and DESIGN.md section 7, "Elastic net", give the algorithm;
+ * attacks.ElasticNetMethod).  x [B,in_h,in_w,in_c]; labels [B] int32 = y, or y_target when `targeted`, or NULL for the model's own
+ * first argmax on x.  decision_rule 0 ("EN") ranks successful iterates by ||d||_2^2 + beta ||d||_1, 1 ("L1") by ||d||_1, d = iterate -
+ * clip(x).  The rate of iteration i is learning_rate * sqrt(1 - i / max_iterations).  Chunks of batch_size images (a trailing partial
+ * chunk is a chunk of its own) share the abort-early decision and nothing else.  Out: x_adv [B,...] = the best successful iterate
+ * over all steps, clip(x) bit for bit where none succeeded; best_dist [B] the rule's criterion there (1e10 when none); best_class [B]
+ * int32 (-1 when none); final_const [B] float64 and chunk_stop [binary_search_steps, ceil(B / batch_size)] int32 as dg_cw's (both may
+ * be NULL).  DG_E_INVALID: a null h, x, x_adv, best_dist or best_class, B < 1, beta < 0, clip_min >= clip_max, max_iterations < 1, a
+ * rule outside {0, 1}, batch_size < 1, binary_search_steps < 0.  Device pointers; the whole attack is enqueued on `stream` with no host
+ * synchronisation and no graph capture; no float atomics, every sum in a fixed order: a repeated call returns the same bits, and a
+ * chunk's images give the same bits alone or inside a larger call.  Per iteration the classifier runs one forward over 2 B rows (the
+ * slack and the iterate) and one backward over B; as for dg_cw they keep running over chunks that have stopped.  The workspace
+ * (about 3 x B x pixels floats, and the handle's activations for 2 B rows) lives in the handle and grows on demand.
+ */
+int dg_ead(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted, int batch_size, float confidence, float beta,
+           int decision_rule, int fista, float learning_rate, int binary_search_steps, int max_iterations, int abort_early,
+           double initial_const, float clip_min, float clip_max, float* x_adv, float* best_dist, int32_t* best_class,
+           double* final_const, int32_t* chunk_stop, void* stream);
+
+/*
  * The path's one collective: every rank projects and classifies its contiguous shard of the image list
  * (no collective on the data path) and ONE all_gather assembles the evaluation message -- per rank `count` int32 words, e.g.
  * [n | labels (cap) | preds (cap) | diffs (cap, float32 bits)] as defensegan_amd/gan_defense.py:model_eval_gan_sharded builds it
