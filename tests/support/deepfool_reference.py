@@ -196,6 +196,12 @@ def decidable(out):
     return ((out["pert_gap"] > tp).all(axis=0) & (out["logit_gap"] > tl).all(axis=0) & (out["cand_gap"] > tl) & (out["final_gap"] > tl))
 
 
+def margin_room(out):
+    """[B]: the smallest decision margin of each image over the threshold ``decidable`` holds it to (decidable is room > 1)."""
+    tp, tl = 4.0 * out["pert_err"], 4.0 * out["logit_err"]
+    return np.minimum.reduce([out["pert_gap"].min(axis=0) / tp, out["logit_gap"].min(axis=0) / tl, out["cand_gap"] / tl, out["final_gap"] / tl])
+
+
 # ---- the input sets the GPU tests use (tests/test_deepfool_cpu.py asserts that at least 75 % of each are decidable) --------------
 def model_of(name, shape=(28, 28, 1)):
     """'F': model F's Conv2D stack, 10 classes; 'lin70': Flatten + Linear(70) + Softmax; 'convlin': Conv + ReLU + Linear(10)."""
@@ -203,19 +209,20 @@ def model_of(name, shape=(28, 28, 1)):
     inp = (None,) + tuple(shape)
     if name == "F":
         return nb.model_f(input_shape=inp)
-    if name == "lin70":
-        return nb.MLP([nb.Flatten(), nb.Linear(70), nb.Softmax()], input_shape=inp)
+    if name.startswith("lin") and name[3:].isdigit():               # 'lin70', and the edge cases' 'lin5', 'lin300', 'lin2049'
+        return nb.MLP([nb.Flatten(), nb.Linear(int(name[3:])), nb.Softmax()], input_shape=inp)
     if name == "convlin":
         return nb.MLP([nb.Conv2D(4, (3, 3), (1, 1), "SAME"), nb.ReLU(), nb.Flatten(), nb.Linear(10), nb.Softmax()], input_shape=inp)
     raise KeyError(name)
 
 
-def images(B, shape, seed):
-    """[B, H, W, C] float32 in [0, 1]; every third image (0, 3, ...) holds exact 0 and 1 pixels (about a quarter each), so the clip binds."""
+def images(B, shape, seed, lo=0.0, hi=1.0):
+    """[B, H, W, C] float32 in [lo, hi] ([0, 1] unless given); every third image (0, 3, ...) holds exact lo and hi pixels (about a
+    quarter each), so the clip binds."""
     rs = np.random.RandomState(seed)
-    x = rs.uniform(0.0, 1.0, (B,) + tuple(shape)).astype(np.float32)
+    x = rs.uniform(lo, hi, (B,) + tuple(shape)).astype(np.float32)
     u = rs.uniform(0.0, 1.0, x.shape)
-    sat = np.where(u < 0.25, 0.0, np.where(u > 0.75, 1.0, x)).astype(np.float32)
+    sat = np.where(u < 0.25, lo, np.where(u > 0.75, hi, x)).astype(np.float32)
     x[::3] = sat[::3]
     return x
 
@@ -243,22 +250,22 @@ def case_inputs(case):
     p = R.init_params(m, c["clf_seed"])
     s = np.float32(c.get("logit_scale", LOGIT_SCALE))
     p[-1] = (p[-1][0] * s, p[-1][1] * s)
-    return m, p, clear_images(m, p, c["B"], c["shape"], c["x_seed"])
+    return m, p, clear_images(m, p, c["B"], c["shape"], c["x_seed"], c.get("lo", 0.0), c.get("hi", 1.0), c.get("pool", 4))
 
 
 MIN_GAP = 0.25              # of the standard deviation of the image's logits
 
 
-def clear_images(model, params, B, shape, seed):
-    """B of ``images(4 B, ...)``, every third still one with exact 0 and 1 pixels, kept in order where the float64 logits at the image
-    have their two largest at least MIN_GAP standard deviations (of that image's logits) apart.  r_tot is proportional to that gap while
+def clear_images(model, params, B, shape, seed, lo=0.0, hi=1.0, pool=4):
+    """B of ``images(pool B, ...)`` (pool = 4 unless the case says otherwise), every third still one with exact lo and hi pixels, kept
+    in order where the float64 logits at the image have their two largest at least MIN_GAP standard deviations (of that image's logits) apart.  r_tot is proportional to that gap while
     the float32 error of a logit is not, so an image that starts almost on a boundary cannot be held to a relative bound on r_norm in
     float32 at all; tests/test_deepfool_cpu.py asserts that the float32 CPU run meets a quarter of the GPU test's bound on what is kept."""
-    pool = images(4 * B, shape, seed)
+    n, pool = pool * B, images(pool * B, shape, seed, lo, hi)
     with torch.no_grad():
         z = logits_fn(model, params)(torch.tensor(pool, dtype=torch.float64)).numpy()
     keep = _top_gap(z) >= MIN_GAP * z.std(axis=1)
-    sat, free = [i for i in range(0, 4 * B, 3) if keep[i]], [i for i in range(4 * B) if i % 3 and keep[i]]
+    sat, free = [i for i in range(0, n, 3) if keep[i]], [i for i in range(n) if i % 3 and keep[i]]
     return np.stack([pool[(sat if i % 3 == 0 else free).pop(0)] for i in range(B)])
 
 
@@ -272,3 +279,81 @@ def case_run(case, max_iter=50, overshoot=0.02):
         m, p, x = case_inputs(case)
         _RUNS[key] = run(m, p, x, RUN_CASES[case]["nc"], overshoot, max_iter, 0.0, 1.0, shadow=torch.float32)
     return _RUNS[key]
+
+
+# ---- the edge cases (tests/test_gpu_deepfool_edges.py; tests/test_deepfool_edges_cpu.py asserts what each choice promises) -----------
+# The grid caps of dg_deepfool.hip and the strides that go with them, as text: a test that tiles its images past a cap reaches the
+# second loop trip only while the cap stands where it was chosen for (tests/support/strided_cases.CAP_SOURCES' way).
+IMAGE_CAP = 65536                    # df_image_grid: one workgroup per image (the step and the final kernel)
+WAVE_CAP = 4096 * 4                  # df_wave_grid: 4096 workgroups of 4 images (select, activity, class)
+CAP_SOURCES = (("dg_deepfool.hip", "unsigned df_wave_grid(int B) { return (unsigned)((B + 3) / 4 < 4096 ? (B + 3) / 4 : 4096); }"),
+               ("dg_deepfool.hip", "unsigned df_image_grid(int B) { return (unsigned)(B < 65536 ? B : 65536); }"),
+               ("dg_deepfool.hip", "for (long long b = blockIdx.x; b < B; b += gridDim.x) {"),
+               ("dg_deepfool.hip", "b += (long long)gridDim.x * 4"),
+               ("dg_deepfool.hip", "for (int j = 1 + tid; j < nc; j += 256) {"),
+               ("dg_deepfool.hip", "constexpr int DEEPFOOL_MAX_CAND = 2048;"))
+
+TILE_B = IMAGE_CAP + 2               # workgroups 0 and 1 of the image-strided kernels take a second image; the wave-strided make 5 trips
+# the base sets that are tiled to TILE_B: 67 images, 65536 % 67 == 10, so workgroup 0 sees base image 0 (a NaN pixel: inactive) and then
+# base image 10, workgroup 1 base images 1 and 11; 4 x 4 is the float4 path, 3 x 3 (P = 9) the scalar one
+TILE_CASES = {
+    "tile4x4": dict(model="lin5", shape=(4, 4, 1), clf_seed=11, x_seed=2, B=67, nc=3, max_iter=4),
+    "tile3x3": dict(model="lin5", shape=(3, 3, 1), clf_seed=12, x_seed=3, B=67, nc=3, max_iter=4),
+}
+# many candidates: pass 2's candidate stride takes its second trip at nc >= 258; DEEPFOOL_MAX_CAND = 2048 is the last nc that runs
+MANY_STEP_CASES = [("lin300", (28, 28, 1), 3, 257), ("lin300", (28, 28, 1), 3, 258), ("lin300", (28, 28, 1), 3, 300),
+                   ("lin2049", (4, 4, 1), 2, 2048)]
+# (with hundreds of classes few images have their two largest logits MIN_GAP apart: a wider pool to keep from.  The seeds were
+# searched on the CPU for margins at least twice what ``decidable`` asks: at 2049 classes on 16 pixels the smallest gap between two
+# neighbouring logits is of the order of four float32 errors, and a draw that clears the bar by a hair on one CPU misses it on another)
+MANY_SEEDS = {"lin300": dict(clf_seed=17, x_seed=1, pool=16), "lin2049": dict(clf_seed=135, x_seed=2468, pool=64)}
+MANY_RUN = dict(model="lin300", shape=(28, 28, 1), clf_seed=17, x_seed=1, pool=16, B=3, nc=300, max_iter=50)
+# a signed range: images in [-1, 1], every third saturated at exactly -1 and +1, clipped to [-1, 1]
+SIGNED_CASE = dict(model="lin10", shape=(4, 4, 1), clf_seed=21, x_seed=6, B=24, nc=10, max_iter=50, lo=-1.0, hi=1.0)
+
+
+def tile_inputs(name):
+    """(model, params, x [67, ...]) of a TILE_CASES entry: case_inputs' draw, then one NaN pixel in image 0."""
+    m, p, x = case_inputs(TILE_CASES[name])
+    x = x.copy()
+    x[0].reshape(-1)[1] = np.nan
+    return m, p, x
+
+
+def edge_run(key, m, p, x, c, overshoot=0.02):
+    """The float64 run with its float32 shadow of an edge case ``c`` on ``x``, computed once per ``key`` and shared (never modified)."""
+    if key not in _RUNS:
+        _RUNS[key] = run(m, p, x, c["nc"], overshoot, c["max_iter"], c.get("lo", 0.0), c.get("hi", 1.0), shadow=torch.float32)
+    return _RUNS[key]
+
+
+# The NaN take-back: a model and an image whose logits are finite at x while the first step lands where float32 overflows.  u and v are
+# orthonormal directions of the 16 pixels, t = u . x, q = v . x.  Three Linear layers, no ReLU between them:
+#     h1 = (S t, S t, 1e3 q),   h2 = (S h1_0, S h1_1, 1e3 h1_2),   S^2 = 1.5e38:  h2_0 = h2_1 = 1.5e38 t is finite below t = 2.27
+#     Z_0 = 4.5e6 - 0.5e6 t,    Z_1 = 1e6 t,    Z_2 = 2e6 q + W (h2_0 - h2_1),    W = 1e6 / 1.5e38
+# At t = 2, q = 0: Z = (3.5e6, 2e6, 0), orig = 0, pert_1 = 1.5e6 / 1.5e6 = 1 along u, pert_2 = 3.5e6 / 2.06e6 = 1.7: the step takes t to 3,
+# where h2_0 = h2_1 = 4.5e38 overflows to +inf and Z_2 subtracts the two infinities.  The seeds' way back multiplies 6.7e-33 by
+# 1.2e19 twice: every partial product is a normal float32 number.  The neighbours have q = 1.5: Z_2 = 3e6 is their nearest boundary,
+# 0.24 away, and t moves by 0.06 only.
+TAKEBACK_S = 1.2247449e19
+
+
+def takeback_case():
+    """(model, params float32, x [3, 4, 4, 1] float32): image 1 is the one whose first step overflows; images 0 and 2 are ordinary."""
+    from defensegan_amd import network_builder as nb
+    m = nb.MLP([nb.Flatten(), nb.Linear(3), nb.Linear(3), nb.Linear(3), nb.Softmax()], input_shape=(None, 4, 4, 1))
+    u = np.full(16, 0.25)
+    v = np.concatenate([np.full(8, 0.25), np.full(8, -0.25)])
+    S = TAKEBACK_S
+    W1 = np.stack([S * u, S * u, 1e3 * v], axis=1)
+    W2 = np.diag([S, S, 1e3])
+    w = 1e6 / 1.5e38
+    W3 = np.array([[-0.25 * w, 0.5 * w, w], [-0.25 * w, 0.5 * w, -w], [0.0, 0.0, 2.0]])
+    p = [(W1.astype(np.float32), np.zeros(3, np.float32)), (W2.astype(np.float32), np.zeros(3, np.float32)),
+         (W3.astype(np.float32), np.array([4.5e6, 0.0, 0.0], np.float32))]
+    rs = np.random.RandomState(8)
+    x = np.empty((3, 16), np.float32)
+    x[1] = 0.5 + rs.uniform(-0.02, 0.02, 16)
+    for i in (0, 2):
+        x[i] = np.concatenate([np.full(8, 0.875), np.full(8, 0.125)]) + rs.uniform(-0.02, 0.02, 16)
+    return m, p, x.reshape(3, 4, 4, 1)

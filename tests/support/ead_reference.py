@@ -147,6 +147,10 @@ def ead(layers, params, x, labels=None, targeted=False, batch_size=1, confidence
 # ---------------------------------------------------------------------------------------------------- the GPU tests' inputs
 # name -> the case: the model of the zoo (init_like_reference(seed = ord(model)), or init given), the image count and shape, how the
 # images are drawn, and the attack's parameters.  "quarters": a quarter of the pixels at exactly 0 and a quarter at exactly 1.
+KAPPA = 0.1                # the edge cases' confidence: of the order of the gap between model F's two largest logits on these images
+# the tiny models' initial_const: their logits and class gradients are of order 1 on 16 pixels, so at _BASE's 100 the first step
+# (lr * const * gradient, about 10) throws every pixel onto a clip bound; at 10 it moves them by about one
+TINY_CONST = 10.0
 _BASE = dict(batch_size=16, beta=1e-2, binary_search_steps=1, abort_early=False, initial_const=100.0, learning_rate=0.1)
 CASES = {
     "one_A": dict(model="A", B=16, kw=dict(_BASE, max_iterations=1)),
@@ -172,6 +176,25 @@ CASES = {
 # the first seed find_seed accepts per case, as found on the CPU (tests/test_ead_cpu.py re-derives every entry)
 SEEDS = dict({name: 0 for name in CASES}, mixed_F=1)
 
+# The edge cases (tests/test_gpu_ead_edges.py; tests/test_ead_edges_cpu.py re-derives their seeds and asserts what each is named for).
+# "tiny<n>": Flatten, Linear(16), ReLU, Linear(n), Softmax on 4 x 4 x 1.  "given_y": untargeted, with labels from the caller that differ
+# from the model's own prediction on about half of the images.
+_TINY = dict(shape=(4, 4, 1), init=5)
+EDGE_CASES = {
+    "kappa_F": dict(model="F", B=16, kw=dict(_BASE, max_iterations=10, confidence=KAPPA)),
+    "kappa_targeted_F": dict(model="F", B=16, targeted=True, kw=dict(_BASE, max_iterations=10, confidence=KAPPA)),
+    # kappa in the ITERATE's hinge reaches nothing but the chunk's loss L, which only the abort check reads: abort_early on, at
+    # abort_F's constant (at 100 every image succeeds at once and the chunks stop where they do without kappa)
+    "kappa_abort_F": dict(model="F", B=32, kw=dict(_BASE, max_iterations=10, abort_early=True, initial_const=10.0, confidence=KAPPA)),
+    "huge_chunk_tiny": dict(_TINY, model="tiny3", B=300, kw=dict(_BASE, batch_size=272, max_iterations=10, abort_early=True, initial_const=TINY_CONST)),
+    "abort_every_F": dict(model="F", B=32, kw=dict(_BASE, max_iterations=6, abort_early=True)),
+    "given_y_F": dict(model="F", B=16, given_y=True, kw=dict(_BASE, max_iterations=5)),
+    "beta0_F": dict(model="F", B=16, kw=dict(_BASE, beta=0.0, max_iterations=5)),
+    "two_class_tiny": dict(_TINY, model="tiny2", B=16, kw=dict(_BASE, max_iterations=5, initial_const=TINY_CONST)),
+}
+CASES.update(EDGE_CASES)
+SEEDS.update({name: 0 for name in EDGE_CASES})
+
 
 def draw_images(case, seed):
     rs = np.random.RandomState(1000 + seed)
@@ -193,11 +216,27 @@ def draw_targets(case, seed, own):
     return ((own + 1 + rs.randint(0, 9, len(own))) % 10).astype(np.int64)
 
 
+def draw_given_labels(case, seed, own):
+    """Untargeted labels from the caller: the model's own prediction on about half of the images, another class on the others."""
+    rs = np.random.RandomState(3000 + seed)
+    other = (own + 1 + rs.randint(0, 9, len(own))) % 10
+    return np.where(rs.uniform(0, 1, len(own)) < 0.5, other, own).astype(np.int64)
+
+
+def case_mlp(case):
+    """The network_builder.MLP of a case (no device is touched before its first use): the zoo's model, or "tiny<n>"."""
+    from defensegan_amd import network_builder as nb
+    inp = (None,) + tuple(case.get("shape", (28, 28, 1)))
+    name = case["model"]
+    if name.startswith("tiny"):
+        return nb.MLP([nb.Flatten(), nb.Linear(16), nb.ReLU(), nb.Linear(int(name[4:])), nb.Softmax()], input_shape=inp)
+    return nb.MODELS[name](input_shape=inp)
+
+
 @functools.lru_cache(maxsize=None)
 def _model_params(model, shape, init):
     """(layers, float32 parameters) of the zoo's model as init_like_reference draws them: no device."""
-    from defensegan_amd import network_builder as nb
-    m = nb.MODELS[model](input_shape=(None,) + tuple(shape))
+    m = case_mlp(dict(model=model, shape=shape))
     m.set_weights = lambda p: None                                  # init_like_reference's own code, the installation left out
     return CW.layers_of(m), m.init_like_reference(seed=init)
 
@@ -205,7 +244,7 @@ def _model_params(model, shape, init):
 def case_model(name):
     """(layers, float32 parameters) of the case: init_like_reference(seed = the case's "init", else ord(model))."""
     c = CASES[name]
-    return _model_params(c["model"], tuple(c.get("shape", (28, 28, 1))), int(c.get("init", ord(c["model"]))))
+    return _model_params(c["model"], tuple(c.get("shape", (28, 28, 1))), int(c["init"] if "init" in c else ord(c["model"])))
 
 
 def params64(params):
@@ -218,16 +257,17 @@ def perturbed(params):
              (np.asarray(b, np.float64) * (1 - 2.0 ** -20)).astype(np.float32).astype(np.float64)) for W, b in params]
 
 
-def run_case(case, seed, layers, params, p64=None):
-    """The float64 reference on the case's draw ``seed``: (x float32, labels or None, out)."""
+def run_case(case, seed, layers, params, p64=None, **override):
+    """The float64 reference on the case's draw ``seed``: (x float32, labels or None, out).  ``override`` replaces attack parameters
+    of the case (the same draw under another confidence, say)."""
     x = draw_images(case, seed)
     p64 = params64(params) if p64 is None else p64
     labels = None
-    if case.get("targeted"):
+    if case.get("targeted") or case.get("given_y"):
         with torch.no_grad():
             own = CW.own_label(CW.logits(layers, params64(params), torch.as_tensor(x.astype(np.float64))).numpy())
-        labels = draw_targets(case, seed, own)
-    out = ead(layers, p64, x.astype(np.float64), labels=labels, targeted=bool(case.get("targeted")), **case["kw"])
+        labels = draw_targets(case, seed, own) if case.get("targeted") else draw_given_labels(case, seed, own)
+    out = ead(layers, p64, x.astype(np.float64), labels=labels, targeted=bool(case.get("targeted")), **dict(case["kw"], **override))
     return x, labels, out
 
 
