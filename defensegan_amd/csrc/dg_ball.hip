@@ -10,7 +10,7 @@
 // One workgroup of 256 threads per image, the workgroups strided over the images, one launch per step.  Thread t owns the
 // vectors t, t + 256, ... of the row (V = 4: float4; V = 1 where P is no multiple of 4 or a pointer is not 16-byte aligned) and sums
 // its terms in index order; a 64-lane __shfl_xor butterfly leaves the wave's sum in every lane, the four wave sums go through
-// LDS and are added in wave order by every thread.  No atomics: an image's norm is one fixed-order float32 sum of its own row and
+// LDS and are added in wave order by every thread (clf_block_sum and the row vector ClfVec: dg_attack_device.h).  No atomics: an image's norm is one fixed-order float32 sum of its own row and
 // does not depend on how many images share the launch.  Every product-sum that is evaluated twice (the re-read path forms d in
 // the reduction and again in the write) is an explicit fma, so both evaluations have the same bits whatever the compiler contracts.
 //
@@ -22,6 +22,7 @@
 
 #include <cstdint>
 
+#include "dg_attack_device.h"
 #include "dg_clf_internal.h"
 
 namespace {
@@ -29,35 +30,7 @@ namespace {
 constexpr int BALL_KEEP = 4;          // floats a thread keeps per stream on the register path (one float4, or four scalars)
 constexpr float BALL_TINY = 1e-12f;
 
-// The sum of `v` over the 256 threads, the same bits in every thread.  `part` is 4 floats of LDS; the trailing barrier lets
-// the next reduction reuse it.
-__device__ __forceinline__ float ball_block_sum(float v, float* part) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float s = ((part[0] + part[1]) + part[2]) + part[3];
-    __syncthreads();
-    return s;
-}
-
 __device__ __forceinline__ float ball_term(float d, int ord, float acc) { return ord == 1 ? acc + fabsf(d) : __fmaf_rn(d, d, acc); }
-
-// V floats at vector index i of a row
-template <int V> struct BallVec;
-template <> struct BallVec<1> {
-    float e[1];
-    __device__ __forceinline__ static BallVec load(const float* p, long long i) { return {{p[i]}}; }
-    __device__ __forceinline__ void store(float* p, long long i) const { p[i] = e[0]; }
-};
-template <> struct BallVec<4> {
-    float e[4];
-    __device__ __forceinline__ static BallVec load(const float* p, long long i) {
-        const float4 q = reinterpret_cast<const float4*>(p)[i];
-        return {{q.x, q.y, q.z, q.w}};
-    }
-    __device__ __forceinline__ void store(float* p, long long i) const { reinterpret_cast<float4*>(p)[i] = make_float4(e[0], e[1], e[2], e[3]); }
-};
 
 template <int V>
 __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__ v, const float* __restrict__ w, int B, long long row_elems,
@@ -69,16 +42,16 @@ __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__
         const float* rw = w ? w + b * row_elems : nullptr;
         float acc = 0.f;
         for (long long i = threadIdx.x; i < nvec; i += 256) {
-            BallVec<V> a = BallVec<V>::load(rv, i);
+            ClfVec<V> a = ClfVec<V>::load(rv, i);
             if (rw) {
-                const BallVec<V> c = BallVec<V>::load(rw, i);
+                const ClfVec<V> c = ClfVec<V>::load(rw, i);
 #pragma unroll
                 for (int j = 0; j < V; ++j) a.e[j] -= c.e[j];
             }
 #pragma unroll
             for (int j = 0; j < V; ++j) acc = ball_term(a.e[j], ord, acc);
         }
-        const float s = ball_block_sum(acc, part);
+        const float s = clf_block_sum(acc, part);
         if (threadIdx.x == 0) out[b] = ord == 1 ? s : sqrtf(s);
     }
 }
@@ -94,33 +67,33 @@ __global__ __launch_bounds__(256) void fgm_norm_step_kernel(const float* __restr
         const float* rg = g + b * row_elems;
         const float* rx = x + b * row_elems;
         float* ro = out + b * row_elems;
-        BallVec<V> kept[NK];
+        ClfVec<V> kept[NK];
         float acc = 0.f;
         if constexpr (KEEP) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 const int i = threadIdx.x + k * 256;
                 if (i < nvec) {
-                    kept[k] = BallVec<V>::load(rg, i);
+                    kept[k] = ClfVec<V>::load(rg, i);
 #pragma unroll
                     for (int j = 0; j < V; ++j) acc = ball_term(kept[k].e[j], ord, acc);
                 }
             }
         } else {
             for (int i = threadIdx.x; i < nvec; i += 256) {
-                const BallVec<V> a = BallVec<V>::load(rg, i);
+                const ClfVec<V> a = ClfVec<V>::load(rg, i);
 #pragma unroll
                 for (int j = 0; j < V; ++j) acc = ball_term(a.e[j], ord, acc);
             }
         }
-        const float s = ball_block_sum(acc, part);
+        const float s = clf_block_sum(acc, part);
         const float scale = eps / fmaxf(BALL_TINY, ord == 1 ? s : sqrtf(s));
         if constexpr (KEEP) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 const int i = threadIdx.x + k * 256;
                 if (i < nvec) {
-                    BallVec<V> o = BallVec<V>::load(rx, i);
+                    ClfVec<V> o = ClfVec<V>::load(rx, i);
 #pragma unroll
                     for (int j = 0; j < V; ++j) o.e[j] = clf_clip(__fmaf_rn(scale, kept[k].e[j], o.e[j]), lo, hi);
                     o.store(ro, i);
@@ -128,8 +101,8 @@ __global__ __launch_bounds__(256) void fgm_norm_step_kernel(const float* __restr
             }
         } else {
             for (int i = threadIdx.x; i < nvec; i += 256) {
-                const BallVec<V> a = BallVec<V>::load(rg, i);
-                BallVec<V> o = BallVec<V>::load(rx, i);
+                const ClfVec<V> a = ClfVec<V>::load(rg, i);
+                ClfVec<V> o = ClfVec<V>::load(rx, i);
 #pragma unroll
                 for (int j = 0; j < V; ++j) o.e[j] = clf_clip(__fmaf_rn(scale, a.e[j], o.e[j]), lo, hi);
                 o.store(ro, i);
@@ -140,10 +113,10 @@ __global__ __launch_bounds__(256) void fgm_norm_step_kernel(const float* __restr
 
 // t of vector i: gsum + g in dg_bpda_step's order, or g
 template <int V>
-__device__ __forceinline__ BallVec<V> ball_t(const float* rg, const float* rs, long long i) {
-    BallVec<V> t = BallVec<V>::load(rg, i);
+__device__ __forceinline__ ClfVec<V> ball_t(const float* rg, const float* rs, long long i) {
+    ClfVec<V> t = ClfVec<V>::load(rg, i);
     if (rs) {
-        const BallVec<V> a = BallVec<V>::load(rs, i);
+        const ClfVec<V> a = ClfVec<V>::load(rs, i);
 #pragma unroll
         for (int j = 0; j < V; ++j) t.e[j] = a.e[j] + t.e[j];
     }
@@ -164,7 +137,7 @@ __global__ __launch_bounds__(256) void ball_step_kernel(const float* __restrict_
         const float* rc = x_cur + off;
         const float* ro = x_orig + off;
         float* rn = x_next + off;
-        BallVec<V> kt[NK], ko[NK];                        // t, then d; x_orig
+        ClfVec<V> kt[NK], ko[NK];                        // t, then d; x_orig
         // ---- ||t||
         float acc = 0.f;
         if constexpr (KEEP) {
@@ -179,12 +152,12 @@ __global__ __launch_bounds__(256) void ball_step_kernel(const float* __restrict_
             }
         } else {
             for (int i = threadIdx.x; i < nvec; i += 256) {
-                const BallVec<V> t = ball_t<V>(rg, rs, i);
+                const ClfVec<V> t = ball_t<V>(rg, rs, i);
 #pragma unroll
                 for (int j = 0; j < V; ++j) acc = __fmaf_rn(t.e[j], t.e[j], acc);
             }
         }
-        const float a = eps_iter / fmaxf(BALL_TINY, sqrtf(ball_block_sum(acc, part)));
+        const float a = eps_iter / fmaxf(BALL_TINY, sqrtf(clf_block_sum(acc, part)));
         // ---- d = (x_k + a t) - x and ||d||
         acc = 0.f;
         if constexpr (KEEP) {
@@ -192,8 +165,8 @@ __global__ __launch_bounds__(256) void ball_step_kernel(const float* __restrict_
             for (int k = 0; k < NK; ++k) {
                 const int i = threadIdx.x + k * 256;
                 if (i < nvec) {
-                    const BallVec<V> xc = BallVec<V>::load(rc, i);
-                    ko[k] = BallVec<V>::load(ro, i);
+                    const ClfVec<V> xc = ClfVec<V>::load(rc, i);
+                    ko[k] = ClfVec<V>::load(ro, i);
 #pragma unroll
                     for (int j = 0; j < V; ++j) {
                         const float d = __fmaf_rn(a, kt[k].e[j], xc.e[j]) - ko[k].e[j];
@@ -204,7 +177,7 @@ __global__ __launch_bounds__(256) void ball_step_kernel(const float* __restrict_
             }
         } else {
             for (int i = threadIdx.x; i < nvec; i += 256) {
-                const BallVec<V> t = ball_t<V>(rg, rs, i), xc = BallVec<V>::load(rc, i), xo = BallVec<V>::load(ro, i);
+                const ClfVec<V> t = ball_t<V>(rg, rs, i), xc = ClfVec<V>::load(rc, i), xo = ClfVec<V>::load(ro, i);
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
                     const float d = __fmaf_rn(a, t.e[j], xc.e[j]) - xo.e[j];
@@ -212,14 +185,14 @@ __global__ __launch_bounds__(256) void ball_step_kernel(const float* __restrict_
                 }
             }
         }
-        const float f = fminf(1.f, eps / fmaxf(BALL_TINY, sqrtf(ball_block_sum(acc, part))));
+        const float f = fminf(1.f, eps / fmaxf(BALL_TINY, sqrtf(clf_block_sum(acc, part))));
         // ---- x_{k+1} = clip(x + f d)
         if constexpr (KEEP) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 const int i = threadIdx.x + k * 256;
                 if (i < nvec) {
-                    BallVec<V> o;
+                    ClfVec<V> o;
 #pragma unroll
                     for (int j = 0; j < V; ++j) o.e[j] = clf_clip(__fmaf_rn(f, kt[k].e[j], ko[k].e[j]), lo, hi);
                     o.store(rn, i);
@@ -227,8 +200,8 @@ __global__ __launch_bounds__(256) void ball_step_kernel(const float* __restrict_
             }
         } else {
             for (int i = threadIdx.x; i < nvec; i += 256) {
-                const BallVec<V> t = ball_t<V>(rg, rs, i), xc = BallVec<V>::load(rc, i), xo = BallVec<V>::load(ro, i);
-                BallVec<V> o;
+                const ClfVec<V> t = ball_t<V>(rg, rs, i), xc = ClfVec<V>::load(rc, i), xo = ClfVec<V>::load(ro, i);
+                ClfVec<V> o;
 #pragma unroll
                 for (int j = 0; j < V; ++j) o.e[j] = clf_clip(__fmaf_rn(f, __fmaf_rn(a, t.e[j], xc.e[j]) - xo.e[j], xo.e[j]), lo, hi);
                 o.store(rn, i);

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "dg_attack_device.h"
 #include "dg_clf_internal.h"
 
 int clf_fail(int code, const char* fmt, ...) {
@@ -123,9 +124,7 @@ __global__ __launch_bounds__(256) void clf_eval_kernel(const float* __restrict__
     if (tid == 0) {
         if (rec && orig && diffs) diffs[b] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)P;
         const float* s = scores + (long long)b * ncls;
-        int best = 0;
-        for (int k = 1; k < ncls; ++k)
-            if (s[k] > s[best]) best = k;
+        const int best = clf_first_argmax(s, ncls);
         if (preds) preds[b] = best;
         if (labels && n_correct && labels[b] == best) atomicAdd(n_correct, 1);
     }
@@ -394,14 +393,14 @@ int dg_clf_destroy(dg_clf* h) {
         if (p) (void)hipFree(p);
     for (float* p : h->gbuf)
         if (p) (void)hipFree(p);
-    cw_release(h->cw);
+    search_release(h->cw);
     train_release(h->tr);
     jac_release(h->jac);
     bpda_release(h->bpda);
     pgd_release(h->pgd);
     critic_release(h->critic);
     deepfool_release(h->deepfool);
-    ead_release(h->ead);
+    search_release(h->ead);
     delete h;
     return DG_OK;
 }

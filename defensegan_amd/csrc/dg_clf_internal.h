@@ -1,7 +1,9 @@
-// The classifier handle as its source files see it (dg_deepfool.hip, the DeepFool loop, and dg_ead.hip, the elastic-net attack, besides those named here): dg_clf.hip (the layers, the evaluation and input-gradient kernels),
-// dg_cw.hip (the Carlini-Wagner attack), dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation), dg_bpda.hip (the BPDA/EOT step), dg_pgd.hip (PGD on the bare
-// classifier), dg_ball.hip (the per-image norms and steps of the L1 / L2 attacks) and dg_critic.hip (the WGAN-GP critic's cost, gradient and step).  Everything here is internal to the library: plain C++
-// under hidden visibility, nothing of it is exported.
+// The classifier handle as its source files see it.  Included by: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
+// dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation), dg_bpda.hip (the BPDA/EOT step), dg_pgd.hip
+// (PGD on the bare classifier), dg_ball.hip (the per-image norms and steps of the L1 / L2 attacks), dg_spsa.hip (SPSA), dg_latent.hip
+// (the latent-space attack), dg_critic.hip (the WGAN-GP critic's cost, gradient and step), dg_deepfool.hip (the DeepFool loop) and,
+// through dg_bsearch.h, dg_cw.hip (the Carlini-Wagner attack) and dg_ead.hip (the elastic-net attack).  Everything here is internal
+// to the library: plain C++ under hidden visibility, nothing of it is exported.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -33,14 +35,13 @@ struct ClfLayer {
     long long features() const { return (long long)oh * ow * oc; }
 };
 
-struct CwWork;       // dg_cw.hip
+struct SearchWork;   // dg_bsearch.h: the workspace of dg_cw.hip and of dg_ead.hip
 struct TrainWork;    // dg_clf_train.hip
 struct JacWork;      // dg_jacobian.hip
 struct BpdaWork;     // dg_bpda.hip
 struct PgdWork;      // dg_pgd.hip
 struct CriticWork;   // dg_critic.hip
 struct DeepfoolWork; // dg_deepfool.hip
-struct EadWork;      // dg_ead.hip
 
 struct dg_clf {
     int device = 0;
@@ -61,14 +62,14 @@ struct dg_clf {
     std::vector<size_t> acts_floats;
     float* gbuf[2] = {nullptr, nullptr};      // gradient ping-pong
     size_t gbuf_floats = 0;
-    CwWork* cw = nullptr;                     // Carlini-Wagner workspace, grown on demand
+    SearchWork* cw = nullptr;                 // Carlini-Wagner workspace, grown on demand
     TrainWork* tr = nullptr;                  // training workspace and Adam state
     JacWork* jac = nullptr;                   // class-gradient seed, grown on demand
     BpdaWork* bpda = nullptr;                 // BPDA's cross-entropy seed, grown on demand
     PgdWork* pgd = nullptr;                   // PGD's seed and its two iterate buffers, grown on demand
     CriticWork* critic = nullptr;             // the WGAN-GP critic's three-batch workspace, grown on demand
     DeepfoolWork* deepfool = nullptr;         // DeepFool's candidates, seeds, iterate rows and per-image state, grown on demand
-    EadWork* ead = nullptr;                   // the elastic-net attack's slack / iterate rows and per-image state, grown on demand
+    SearchWork* ead = nullptr;               // the elastic-net attack's slack / iterate rows and per-image state, grown on demand
 
     int pixels() const { return in_h * in_w * in_c; }
 };
@@ -114,14 +115,13 @@ int clf_kept_forward(dg_clf* h, const float* x, int B, hipStream_t s);
 // dLoss/dx from the seed dLoss/dlogits [B, n] after clf_kept_forward of the same B images; *grad lies in h->gbuf, never in seed.
 int clf_seeded_backward(dg_clf* h, const float* seed, int B, hipStream_t s, float** grad);
 
-void cw_release(CwWork* w);          // dg_cw.hip
+void search_release(SearchWork* w); // dg_cw.hip, for h->cw and h->ead
 void train_release(TrainWork* w);    // dg_clf_train.hip
 void jac_release(JacWork* w);        // dg_jacobian.hip
 void bpda_release(BpdaWork* w);      // dg_bpda.hip
 void pgd_release(PgdWork* w);        // dg_pgd.hip
 void critic_release(CriticWork* w);  // dg_critic.hip
 void deepfool_release(DeepfoolWork* w);   // dg_deepfool.hip
-void ead_release(EadWork* w);        // dg_ead.hip
 
 // ---- dg_clf_train.hip -------------------------------------------------------------------------------------------------------------
 // How a Conv2D / Linear layer's weight gradient over B images is cut: `slots` runs of kc terms of its reduction axis, each slot
@@ -139,7 +139,7 @@ void train_launch_wgrad(const ClfLayer& v, const float* x, const float* g, const
 // and the step count.  Fetch them per call: adding a layer moves them.
 int train_adam_state(dg_clf* h, float*** m, float*** v, long long** t);
 
-// ---- shared by the attack steps (dg_bpda.hip, dg_ball.hip, dg_spsa.hip) -------------------------------------------------------------------------
+// ---- shared by the attack steps (dg_bpda.hip, dg_ball.hip, dg_spsa.hip, dg_deepfool.hip, dg_ead.hip; dg_attack_device.h has the reductions) ----
 // the final clip of every attack step: clip(v, lo, hi) with lo <= hi
 __device__ __forceinline__ float clf_clip(float v, float lo, float hi) {
     v = v < lo ? lo : v;

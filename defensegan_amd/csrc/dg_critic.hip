@@ -31,6 +31,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "dg_attack_device.h"
 #include "dg_clf_internal.h"
 
 struct CriticWork {
@@ -66,17 +67,6 @@ __global__ __launch_bounds__(256) void critic_interp_kernel(const float* __restr
     }
 }
 
-// the sum of `v` over the 256 threads, the same bits in every thread; `red` is 4 floats of LDS, free again on return
-__device__ __forceinline__ float critic_block_sum(float v, float* red) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float s = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return s;
-}
-
 // v's factor of g: coef (s - 1) / s with coef = lambda 2 / N; 0 where s == 0 (and where lambda is 0)
 __device__ __forceinline__ float critic_factor(float s, float coef) { return (s > 0.f && coef != 0.f) ? coef * ((s - 1.0f) / s) : 0.f; }
 
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(256) void critic_norm_kernel(const float* __restric
         if constexpr (IMAGE) {
             float acc = 0.f;
             for (long long i = threadIdx.x; i < P; i += 256) acc = __fmaf_rn(gb[i], gb[i], acc);
-            const float s = sqrtf(critic_block_sum(acc, red));
+            const float s = sqrtf(clf_block_sum(acc, red));
             const float f = critic_factor(s, coef);
             for (long long i = threadIdx.x; i < P; i += 256) vb[i] = f * gb[i];
             if (threadIdx.x == 0) {
@@ -115,7 +105,7 @@ __global__ __launch_bounds__(256) void critic_norm_kernel(const float* __restric
                 if (slopes) slopes[b * WC + col] = s;
                 mine = __fmaf_rn(s - 1.0f, s - 1.0f, mine);
             }
-            const float tot = critic_block_sum(mine, red);
+            const float tot = clf_block_sum(mine, red);
             if (threadIdx.x == 0) pen[b] = tot;
         }
     }

@@ -45,70 +45,34 @@
 
 #include <cstdint>
 
-#include "dg_clf_internal.h"
+#include "dg_attack_device.h"
+#include "dg_bsearch.h"
 #include "dg_shared_math.h"
-
-struct CwWork {
-    char* mem = nullptr;
-    size_t bytes = 0;
-};
 
 namespace {
 
-// the workspace, carved from one allocation: N x P planes, the seed, per-image and per-chunk scalars
-struct CwBufs {
+// the workspace, carved from one allocation: the search state (best = bestl2, obest = o_bestl2) and the N x P planes
+struct CwBufs : SearchBufs {
     float *w, *m, *v, *timg, *other, *newimg;      // [N, P]
-    float* seed;                                   // [N, n] dloss1/dlogits
-    float *l2, *loss1, *bestl2, *obestl2;          // [N]
-    double *cst, *lower, *upper;                   // [N]
-    int32_t *lab, *score, *succ, *bestscore, *obestscore, *improved;   // [N]
-    double* prev;                                  // [chunks]
-    int32_t* abort_iter;                           // [chunks]: -1 running, else the iteration whose check stopped the chunk
+    float* l2;                                     // [N]
 };
 
 size_t carve(CwBufs* b, char* base, long long N, long long P, long long n, long long chunks) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
-    const size_t plane = (size_t)(N * P) * sizeof(float);
-    b->w = (float*)take(plane); b->m = (float*)take(plane); b->v = (float*)take(plane);
-    b->timg = (float*)take(plane); b->other = (float*)take(plane); b->newimg = (float*)take(plane);
-    b->seed = (float*)take((size_t)(N * n) * sizeof(float));
-    b->l2 = (float*)take(N * sizeof(float)); b->loss1 = (float*)take(N * sizeof(float));
-    b->bestl2 = (float*)take(N * sizeof(float)); b->obestl2 = (float*)take(N * sizeof(float));
-    b->cst = (double*)take(N * sizeof(double)); b->lower = (double*)take(N * sizeof(double)); b->upper = (double*)take(N * sizeof(double));
-    b->lab = (int32_t*)take(N * 4); b->score = (int32_t*)take(N * 4); b->succ = (int32_t*)take(N * 4);
-    b->bestscore = (int32_t*)take(N * 4); b->obestscore = (int32_t*)take(N * 4); b->improved = (int32_t*)take(N * 4);
-    b->prev = (double*)take(chunks * sizeof(double));
-    b->abort_iter = (int32_t*)take(chunks * 4);
-    return off;
+    SearchCarver c{base};
+    for (float** p : {&b->w, &b->m, &b->v, &b->timg, &b->other, &b->newimg}) *p = c.take<float>((size_t)(N * P));
+    b->l2 = c.take<float>(N);
+    search_carve(b, c, N, n, chunks);
+    return c.off;
 }
 
 __device__ __forceinline__ float cw_to_img(float t, float lo, float hi) { return (t + 1.0f) * 0.5f * (hi - lo) + lo; }
-
-__device__ __forceinline__ int first_argmax(const float* z, int n) {
-    int best = 0;
-    for (int k = 1; k < n; ++k)
-        if (z[k] > z[best]) best = k;
-    return best;
-}
 
 // once per call, one workgroup per image: the label, timg, other, x_adv = clip(x), the per-image constants and outer bests
 __global__ __launch_bounds__(256) void cw_setup_kernel(const float* __restrict__ x, const int32_t* __restrict__ labels,
                                                         const float* __restrict__ logits, int n, long long P, float lo, float hi,
                                                         double initial_const, CwBufs bf, float* __restrict__ xadv) {
     const long long b = blockIdx.x;
-    if (threadIdx.x == 0) {
-        bf.lab[b] = labels ? labels[b] : first_argmax(logits + b * n, n);
-        bf.obestl2[b] = 1e10f;
-        bf.obestscore[b] = -1;
-        bf.cst[b] = initial_const;
-        bf.lower[b] = 0.0;
-        bf.upper[b] = 1e10;
-    }
+    if (threadIdx.x == 0) search_setup(bf, b, labels, logits, n, initial_const);
     const float* xb = x + b * P;
     for (long long i = threadIdx.x; i < P; i += 256) {
         const float xv = xb[i];
@@ -128,25 +92,8 @@ __global__ __launch_bounds__(256) void cw_reset_kernel(CwBufs bf, long long P, i
                                                         int targeted, float lo, float hi) {
     const long long b = blockIdx.x;
     if (threadIdx.x == 0) {
-        if (update) {
-            const int bs = bf.bestscore[b], t = bf.lab[b];
-            const double c = bf.cst[b];
-            if (bs != -1 && (targeted ? bs == t : bs != t)) {
-                bf.upper[b] = fmin(bf.upper[b], c);
-                if (bf.upper[b] < 1e9) bf.cst[b] = (bf.lower[b] + bf.upper[b]) / 2;
-            } else {
-                bf.lower[b] = fmax(bf.lower[b], c);
-                bf.cst[b] = bf.upper[b] < 1e9 ? (bf.lower[b] + bf.upper[b]) / 2 : c * 10;
-            }
-        }
-        if (!reset) return;
-        if (repeat_last) bf.cst[b] = bf.upper[b];
-        bf.bestl2[b] = 1e10f;
-        bf.bestscore[b] = -1;
-        if (b % batch_size == 0) {
-            bf.prev[b / batch_size] = 1e6;
-            bf.abort_iter[b / batch_size] = -1;
-        }
+        if (update) search_update_const(bf, b, targeted);
+        if (reset) search_reset_scalars(bf, b, batch_size, repeat_last);
     }
     if (!reset) return;
     for (long long i = threadIdx.x; i < P; i += 256) {
@@ -158,7 +105,9 @@ __global__ __launch_bounds__(256) void cw_reset_kernel(CwBufs bf, long long P, i
     }
 }
 
-// (a) one workgroup per image: l2 (fixed-order block reduction), loss1, the seed dloss1/dZ, success and argmax
+// (a) one workgroup per image: l2 (fixed-order block reduction), loss1, the seed dloss1/dZ, success and argmax.  l2 adds the four
+// wave sums as (p0 + p1) + (p2 + p3), NOT in clf_block_sum's order: deliberate, tests/support/cw_reference.py pins this association
+// and another one changes bits.
 __global__ __launch_bounds__(256) void cw_head_kernel(const float* __restrict__ logits, int n, long long P, int batch_size, int targeted,
                                                        float confidence, CwBufs bf) {
     __shared__ float red[4];
@@ -176,8 +125,7 @@ __global__ __launch_bounds__(256) void cw_head_kernel(const float* __restrict__ 
         const float d = ni[i] - ot[i];
         sq = __builtin_fmaf(d, d, sq);
     }
-#pragma unroll
-    for (int msk = 32; msk >= 1; msk >>= 1) sq += __shfl_xor(sq, msk, 64);
+    sq = clf_wave_sum(sq);
     if (lane == 0) red[wave] = sq;
     __syncthreads();
     if (tid != 0) return;
@@ -189,82 +137,23 @@ __global__ __launch_bounds__(256) void cw_head_kernel(const float* __restrict__ 
         bf.l2[b] = l2;
         bf.loss1[b] = 0.f;
         bf.succ[b] = 0;
-        bf.score[b] = first_argmax(z, n);
+        bf.score[b] = clf_first_argmax(z, n);
         return;
     }
-    const float real = z[t];
-    float oth = -3.402823466e38f;
-    for (int k = 0; k < n; ++k) {
-        const float o = k == t ? -10000.0f : z[k];
-        oth = o > oth ? o : oth;
-    }
-    int cnt = 0;
-    for (int k = 0; k < n; ++k) cnt += ((k == t ? -10000.0f : z[k]) == oth) ? 1 : 0;
     const float c = (float)bf.cst[b];
-    const float arg = targeted ? (oth - real + confidence) : (real - oth + confidence);
-    const float loss1 = c * (arg > 0.f ? arg : 0.f);
-    for (int k = 0; k < n; ++k) sd[k] = 0.f;
-    if (arg > 0.f) {
-        const float sgn = targeted ? -1.0f : 1.0f;
-        const float share = (1.0f / (float)cnt) * (-sgn * c);
-        for (int k = 0; k < n; ++k)
-            if (k != t && z[k] == oth) sd[k] = share;
-        sd[t] = sgn * c;
-    }
-    // success on Z' (label entry moved by the confidence), the recorded score on Z itself
-    int am = 0;
-    float best = t == 0 ? (targeted ? z[0] - confidence : z[0] + confidence) : z[0];
-    for (int k = 1; k < n; ++k) {
-        const float zk = k == t ? (targeted ? z[k] - confidence : z[k] + confidence) : z[k];
-        if (zk > best) { best = zk; am = k; }
-    }
+    float oth;
+    const float arg = cw_hinge_arg(z, n, t, targeted, confidence, &oth);
+    cw_hinge_seed(sd, z, n, t, targeted, c, arg, oth);
     bf.l2[b] = l2;
-    bf.loss1[b] = loss1;
-    bf.succ[b] = targeted ? (am == t) : (am != t);
-    bf.score[b] = first_argmax(z, n);
+    bf.loss1[b] = c * (arg > 0.f ? arg : 0.f);
+    bf.succ[b] = cw_success(z, n, t, targeted, confidence);          // on Z' (the label's entry moved by the confidence)
+    bf.score[b] = clf_first_argmax(z, n);                            // on Z itself
 }
 
 // (b) one workgroup per chunk: the chunk's loss in a fixed order, the abort decision on check iterations, best tracking
 __global__ __launch_bounds__(256) void cw_chunk_kernel(CwBufs bf, int N, int batch_size, int iter, int check) {
-    __shared__ int abort_now, stopped;
-    const int c = blockIdx.x;
-    const int first = c * batch_size;
-    const int cnt = N - first < batch_size ? N - first : batch_size;
-    // thread 0 alone reads and writes the chunk's abort state; the others learn it after the barrier (a read of abort_iter by
-    // another wave could otherwise see this iteration's write and skip the "improved" flags the update kernel still reads)
-    if (threadIdx.x == 0) {
-        stopped = bf.abort_iter[c] >= 0;
-        abort_now = 0;
-        if (!stopped && check) {
-            double L = 0.0;
-            for (int j = 0; j < cnt; ++j) L += (double)bf.loss1[first + j] + (double)bf.l2[first + j];
-            if (L > bf.prev[c] * 0.9999) {
-                bf.abort_iter[c] = iter;
-                abort_now = 1;
-            } else {
-                bf.prev[c] = L;
-            }
-        }
-    }
-    __syncthreads();
-    if (stopped) return;
-    for (int j = threadIdx.x; j < cnt; j += 256) {
-        const int b = first + j;
-        int imp = 0;
-        if (!abort_now && bf.succ[b]) {
-            const float l2 = bf.l2[b];
-            if (l2 < bf.bestl2[b]) {
-                bf.bestl2[b] = l2;
-                bf.bestscore[b] = bf.score[b];
-            }
-            if (l2 < bf.obestl2[b]) {
-                bf.obestl2[b] = l2;
-                bf.obestscore[b] = bf.score[b];
-                imp = 1;
-            }
-        }
-        bf.improved[b] = imp;
-    }
+    search_chunk(
+        bf, N, batch_size, iter, check, [&](int b) { return (double)bf.loss1[b] + (double)bf.l2[b]; }, [&](int b) { return bf.l2[b]; });
 }
 
 // (c) elementwise: x_adv = newimg where the image improved, then the gradient through tanh, TF Adam, the next w and newimg
@@ -291,7 +180,7 @@ __global__ __launch_bounds__(256) void cw_update_kernel(CwBufs bf, const float* 
 
 }  // namespace
 
-void cw_release(CwWork* w) {
+void search_release(SearchWork* w) {
     if (!w) return;
     if (w->mem) (void)hipFree(w->mem);
     delete w;
@@ -313,8 +202,7 @@ int dg_cw(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted,
     const long long N = B, P = h->pixels(), chunks = (N + batch_size - 1) / batch_size;
     CwBufs bf;
     const size_t need = carve(&bf, nullptr, N, P, n, chunks);
-    if (!h->cw) h->cw = new CwWork();
-    int rc = clf_grow(&h->cw->mem, 1, h->cw->bytes, need);
+    int rc = search_workspace(&h->cw, need);
     if (rc) return rc;
     carve(&bf, h->cw->mem, N, P, n, chunks);
 
@@ -325,11 +213,10 @@ int dg_cw(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted,
     CLF_TRY(hipGetLastError());
     const long long total = N * P;
     const unsigned egrid = (unsigned)((total + 255) / 256);
-    const int every = max_iterations / 10 > 0 ? max_iterations / 10 : 1;
+    const int every = search_every(max_iterations);
     for (int step = 0; step < binary_search_steps; ++step) {
-        const int repeat_last = (binary_search_steps >= 10 && step == binary_search_steps - 1) ? 1 : 0;
-        hipLaunchKernelGGL(cw_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, P, batch_size, step > 0 ? 1 : 0, 1, repeat_last,
-                           targeted ? 1 : 0, lo, hi);
+        hipLaunchKernelGGL(cw_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, P, batch_size, step > 0 ? 1 : 0, 1,
+                           search_repeat_last(binary_search_steps, step), targeted ? 1 : 0, lo, hi);
         for (int it = 0; it < max_iterations; ++it) {
             if ((rc = clf_kept_forward(h, bf.newimg, B, s))) return rc;
             hipLaunchKernelGGL(cw_head_kernel, dim3((unsigned)N), dim3(256), 0, s, h->acts[h->logit_layer], n, P, batch_size, targeted ? 1 : 0,
@@ -342,18 +229,11 @@ int dg_cw(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted,
                                dg_tf_adam_lr(learning_rate, it + 1), lo, hi);
             CLF_TRY(hipGetLastError());
         }
-        if (chunk_stop)
-            CLF_TRY(hipMemcpyAsync(chunk_stop + (long long)step * chunks, bf.abort_iter, chunks * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        if ((rc = search_copy_chunk_stop(bf, chunk_stop, step, chunks, s))) return rc;
     }
-    if (final_const) {
-        if (binary_search_steps > 0)
-            hipLaunchKernelGGL(cw_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, P, batch_size, 1, 0, 0, targeted ? 1 : 0, lo, hi);
-        CLF_TRY(hipGetLastError());
-        CLF_TRY(hipMemcpyAsync(final_const, bf.cst, N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    if (best_l2) CLF_TRY(hipMemcpyAsync(best_l2, bf.obestl2, N * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (best_class) CLF_TRY(hipMemcpyAsync(best_class, bf.obestscore, N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    return DG_OK;
+    if (final_const && binary_search_steps > 0)          // the last step's constant update alone: cleverhans' final constants
+        hipLaunchKernelGGL(cw_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, P, batch_size, 1, 0, 0, targeted ? 1 : 0, lo, hi);
+    return search_copy_out(bf, N, final_const, best_l2, best_class, s);
 }
 
 }  // extern "C"

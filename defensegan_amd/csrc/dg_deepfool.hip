@@ -14,7 +14,7 @@
 // minimum; an image without a minimum becomes inactive and keeps its r_b (the iteration still counts in iters).  An image whose
 // logits hold a NaN -- at x_b, or at the adv_b a step has just produced -- becomes inactive, and a step that produced one is taken
 // back: the image returns clip(x_b + (1 + overshoot) r_b) from the last finite state.  A NaN is never a candidate for final_class
-// (dg_pgd's scan: class 0 where class 0 is a NaN or nothing else is left).
+// (clf_wave_class: class 0 where class 0 is a NaN or nothing else is left).
 //
 // One iteration is: the class gradients of all nc candidates, the step (deepfool_step_kernel, one workgroup per image), one kept
 // forward at the new adv, the activity kernel.  The class gradients come from the classifier's own chain (dg_clf_internal.h) and
@@ -38,6 +38,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "dg_attack_device.h"
 #include "dg_clf_internal.h"
 
 #ifdef DG_MEASURE
@@ -81,45 +82,6 @@ namespace {
 constexpr int DEEPFOOL_CHECK = 2;            // iterations between two reads of the active count
 constexpr int DEEPFOOL_MAX_CAND = 2048;      // 5 floats of LDS per candidate in the step kernel
 
-// V floats at vector index i of a row (dg_ball.hip's BallVec)
-template <int V> struct DfVec;
-template <> struct DfVec<1> {
-    float e[1];
-    __device__ __forceinline__ static DfVec load(const float* p, long long i) { return {{p[i]}}; }
-    __device__ __forceinline__ void store(float* p, long long i) const { p[i] = e[0]; }
-};
-template <> struct DfVec<4> {
-    float e[4];
-    __device__ __forceinline__ static DfVec load(const float* p, long long i) {
-        const float4 q = reinterpret_cast<const float4*>(p)[i];
-        return {{q.x, q.y, q.z, q.w}};
-    }
-    __device__ __forceinline__ void store(float* p, long long i) const { reinterpret_cast<float4*>(p)[i] = make_float4(e[0], e[1], e[2], e[3]); }
-};
-
-// The first arg-max of r[0 .. n) by one wave, the classes strided over its lanes, the same answer in every lane: each lane keeps the
-// first maximum of its classes, a butterfly keeps the larger value and, of equal values, the smaller class.  A NaN is never a
-// candidate (pgd_track_kernel's scan); INT_MAX when nothing is left.  *nan: whether the row holds a NaN.
-__device__ __forceinline__ int df_wave_argmax(const float* r, int n, int lane, bool* nan) {
-    float best = -__builtin_inff();
-    int arg = INT_MAX;
-    int bad = 0;
-    for (int c = lane; c < n; c += 64) {
-        const float v = r[c];
-        if (v != v) bad = 1;
-        else if (arg == INT_MAX || v > best) { best = v; arg = c; }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ob = __shfl_xor(best, m, 64);
-        const int oa = __shfl_xor(arg, m, 64);
-        bad |= __shfl_xor(bad, m, 64);
-        if (oa != INT_MAX && (arg == INT_MAX || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
-    }
-    *nan = bad != 0;
-    return arg;
-}
-
 // rows[(b copies + c), :] = x[b, :], one thread per element written
 __global__ __launch_bounds__(256) void df_replicate_kernel(const float* __restrict__ x, float* __restrict__ rows, long long total, int P, int copies) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -148,18 +110,7 @@ __global__ __launch_bounds__(256) void df_select_kernel(const float* __restrict_
         int pa = -1;                                            // round t - 1's pick; none before round 0
         for (int t = 0; t < nc; ++t) {
             float best = 0.f;
-            int arg = INT_MAX;
-            for (int c = lane; c < n; c += 64) {
-                const float v = r[c];
-                const bool after = pa < 0 ? (v == v) : (v < pv || (v == pv && c > pa));
-                if (after && (arg == INT_MAX || v > best)) { best = v; arg = c; }
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const float ob = __shfl_xor(best, m, 64);
-                const int oa = __shfl_xor(arg, m, 64);
-                if (oa != INT_MAX && (arg == INT_MAX || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
-            }
+            int arg = clf_wave_argmax_if(r, n, lane, best, [&](float v, int c) { return pa < 0 ? (v == v) : (v < pv || (v == pv && c > pa)); });
             if (arg == INT_MAX) { arg = 0; best = -__builtin_inff(); }          // uniform over the wave; only with a NaN in the row
             if (lane == 0) cand[b * nc + t] = arg;
             pv = best;
@@ -220,15 +171,14 @@ __global__ __launch_bounds__(256) void deepfool_step_kernel(const float* __restr
             const float* gjp = grads + (b * gb + j * gj) * P;
             float acc = 0.f;
             for (long long i = tid; i < nvec; i += 256) {
-                const DfVec<V> a = DfVec<V>::load(gjp, i), c = DfVec<V>::load(g0, i);
+                const ClfVec<V> a = ClfVec<V>::load(gjp, i), c = ClfVec<V>::load(g0, i);
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
                     const float d = a.e[e] - c.e[e];
                     acc = __fmaf_rn(d, d, acc);
                 }
             }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+            acc = clf_wave_sum(acc);
             if (lane == 0) part[4 * j + wave] = acc;
         }
         __syncthreads();
@@ -262,8 +212,8 @@ __global__ __launch_bounds__(256) void deepfool_step_kernel(const float* __restr
         const float* rold = (sel ? r1 : r0) + b * P;
         float* rnew = (sel ? r0 : r1) + b * P;
         for (long long i = tid; i < nvec; i += 256) {
-            const DfVec<V> a = DfVec<V>::load(gs, i), c = DfVec<V>::load(g0, i), ro = DfVec<V>::load(rold, i), xo = DfVec<V>::load(rx, i);
-            DfVec<V> rn, av;
+            const ClfVec<V> a = ClfVec<V>::load(gs, i), c = ClfVec<V>::load(g0, i), ro = ClfVec<V>::load(rold, i), xo = ClfVec<V>::load(rx, i);
+            ClfVec<V> rn, av;
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 rn.e[e] = __fmaf_rn(coef, a.e[e] - c.e[e], ro.e[e]);
@@ -287,7 +237,7 @@ __global__ __launch_bounds__(256) void df_activity_kernel(const float* __restric
     for (long long b = (long long)blockIdx.x * 4 + wave; b < B; b += (long long)gridDim.x * 4) {
         if (!active[b]) continue;                               // uniform over the wave
         bool nan;
-        const int arg = df_wave_argmax(logits + b * row_step * n, n, lane, &nan);
+        const int arg = clf_wave_argmax(logits + b * row_step * n, n, lane, &nan);
         if (lane == 0) {
             if (nan) {
                 active[b] = 0;
@@ -302,7 +252,7 @@ __global__ __launch_bounds__(256) void df_activity_kernel(const float* __restric
 }
 
 // x_adv_b = clip(x_b + (1 + overshoot) r_b, lo, hi) and r_norm_b = ||x_adv_b - x_b||_2, the distance of what was written: thread t's
-// terms in index order, the wave butterfly, the four wave sums in wave order (dg_ball.hip's block sum).  x_adv may be x.
+// terms in index order, then clf_block_sum (dg_attack_device.h).  x_adv may be x.
 template <int V>
 __global__ __launch_bounds__(256) void deepfool_final_kernel(const float* x, const float* __restrict__ r0, const float* __restrict__ r1,
                                                               const int32_t* __restrict__ rsel, float* x_adv, float* __restrict__ r_norm, int B, int P,
@@ -316,8 +266,8 @@ __global__ __launch_bounds__(256) void deepfool_final_kernel(const float* x, con
         float* ro = x_adv + b * P;
         float acc = 0.f;
         for (long long i = tid; i < nvec; i += 256) {
-            const DfVec<V> xo = DfVec<V>::load(rx, i), rv = DfVec<V>::load(rr, i);
-            DfVec<V> o;
+            const ClfVec<V> xo = ClfVec<V>::load(rx, i), rv = ClfVec<V>::load(rr, i);
+            ClfVec<V> o;
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 o.e[e] = clf_clip(__fmaf_rn(scale, rv.e[e], xo.e[e]), lo, hi);
@@ -326,12 +276,8 @@ __global__ __launch_bounds__(256) void deepfool_final_kernel(const float* x, con
             }
             o.store(ro, i);
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-        if ((tid & 63) == 0) df_lds[tid >> 6] = acc;
-        __syncthreads();
-        if (tid == 0 && r_norm) r_norm[b] = sqrtf(((df_lds[0] + df_lds[1]) + df_lds[2]) + df_lds[3]);
-        __syncthreads();
+        const float s = clf_block_sum(acc, df_lds);
+        if (tid == 0 && r_norm) r_norm[b] = sqrtf(s);
     }
 }
 
@@ -339,10 +285,7 @@ __global__ __launch_bounds__(256) void deepfool_final_kernel(const float* x, con
 __global__ __launch_bounds__(256) void df_class_kernel(const float* __restrict__ logits, int n, int B, int32_t* __restrict__ out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (long long b = (long long)blockIdx.x * 4 + wave; b < B; b += (long long)gridDim.x * 4) {
-        const float* r = logits + b * n;
-        bool nan;
-        int arg = df_wave_argmax(r, n, lane, &nan);
-        if (r[0] != r[0] || arg == INT_MAX) arg = 0;
+        const int arg = clf_wave_class(logits + b * n, n, lane);
         if (lane == 0) out[b] = arg;
     }
 }

@@ -42,7 +42,7 @@
 // per chunk: L, the abort decision, best tracking, the "improved" flag; (c) ead_slack_head_kernel on the Y half: the logit seed; the
 // seeded backward (dg_clf.hip's chain, unchanged); (d) ead_update_kernel, one workgroup per image: x_adv = X where improved, then
 // S, X', Y' and l1 / l2 of X' in one pass over the image (thread t sums its elements t, t + 256, ... in order, then the block in
-// critic_block_sum's order).  (e) ead_reset_kernel once per outer step.  No host synchronisation, copy or decision inside the
+// clf_block_sum's order).  (e) ead_reset_kernel once per outer step.  No host synchronisation, copy or decision inside the
 // call, no graph capture, no float atomics.  As in dg_cw the classifier kernels know no chunks and keep running over stopped
 // chunks; (a) to (d) return at once for them.  gfx950 only.
 #include <hip/hip_runtime.h>
@@ -50,75 +50,27 @@
 #include <cmath>
 #include <cstdint>
 
-#include "dg_clf_internal.h"
-
-struct EadWork {
-    char* mem = nullptr;
-    size_t bytes = 0;
-};
+#include "dg_attack_device.h"
+#include "dg_bsearch.h"
 
 namespace {
 
-// the workspace, carved from one allocation
-struct EadBufs {
+// the workspace, carved from one allocation: the search state (seed = const * dloss1_Y/dlogits, loss1 = const * loss1_X, best /
+// obest by the decision rule's criterion) and the rows
+struct EadBufs : SearchBufs {
     float* xy;                                     // [2 N, P]: rows 0 .. N the slack Y, rows N .. 2 N the iterate X
     float* x0;                                     // [N, P] clip(x)
-    float* seed;                                   // [N, n] const * dloss1_Y/dlogits
-    float *l1, *l2, *loss1, *best, *obest;         // [N]; loss1 = const * loss1_X
-    double *cst, *lower, *upper;                   // [N]
-    int32_t *lab, *score, *succ, *bestscore, *obestscore, *improved;   // [N]
-    double* prev;                                  // [chunks]
-    int32_t* abort_iter;                           // [chunks]: -1 running, else the iteration whose check stopped the chunk
+    float *l1, *l2;                                // [N]
 };
 
 size_t carve(EadBufs* b, char* base, long long N, long long P, long long n, long long chunks) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
-    const size_t plane = (size_t)(N * P) * sizeof(float);
-    b->xy = (float*)take(2 * plane);
-    b->x0 = (float*)take(plane);
-    b->seed = (float*)take((size_t)(N * n) * sizeof(float));
-    b->l1 = (float*)take(N * sizeof(float)); b->l2 = (float*)take(N * sizeof(float)); b->loss1 = (float*)take(N * sizeof(float));
-    b->best = (float*)take(N * sizeof(float)); b->obest = (float*)take(N * sizeof(float));
-    b->cst = (double*)take(N * sizeof(double)); b->lower = (double*)take(N * sizeof(double)); b->upper = (double*)take(N * sizeof(double));
-    b->lab = (int32_t*)take(N * 4); b->score = (int32_t*)take(N * 4); b->succ = (int32_t*)take(N * 4);
-    b->bestscore = (int32_t*)take(N * 4); b->obestscore = (int32_t*)take(N * 4); b->improved = (int32_t*)take(N * 4);
-    b->prev = (double*)take(chunks * sizeof(double));
-    b->abort_iter = (int32_t*)take(chunks * 4);
-    return off;
-}
-
-__device__ __forceinline__ int ead_first_argmax(const float* z, int n) {
-    int best = 0;
-    for (int k = 1; k < n; ++k)
-        if (z[k] > z[best]) best = k;
-    return best;
-}
-
-// the hinge's argument on the logits z for the label t in [0, n): real - oth + kappa (targeted: oth - real + kappa); *oth_out = oth
-__device__ __forceinline__ float ead_hinge_arg(const float* z, int n, int t, int targeted, float kappa, float* oth_out) {
-    float oth = -3.402823466e38f;
-    for (int k = 0; k < n; ++k) {
-        const float o = k == t ? -10000.0f : z[k];
-        oth = o > oth ? o : oth;
-    }
-    *oth_out = oth;
-    return targeted ? (oth - z[t] + kappa) : (z[t] - oth + kappa);
-}
-
-// the fixed-order block sum of dg_critic.hip's critic_block_sum: the wave by xor-shuffles, then the four waves left to right
-__device__ __forceinline__ float ead_block_sum(float v, float* red) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float s = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return s;
+    SearchCarver c{base};
+    b->xy = c.take<float>((size_t)(2 * N * P));
+    b->x0 = c.take<float>((size_t)(N * P));
+    b->l1 = c.take<float>(N);
+    b->l2 = c.take<float>(N);
+    search_carve(b, c, N, n, chunks);
+    return c.off;
 }
 
 // once per call, one workgroup per image: the label, x0 = x_adv = clip(x), the per-image constants and outer bests
@@ -126,14 +78,7 @@ __global__ __launch_bounds__(256) void ead_setup_kernel(const float* __restrict_
                                                          const float* __restrict__ logits, int n, long long P, float lo, float hi,
                                                          double initial_const, EadBufs bf, float* __restrict__ xadv) {
     const long long b = blockIdx.x;
-    if (threadIdx.x == 0) {
-        bf.lab[b] = labels ? labels[b] : ead_first_argmax(logits + b * n, n);
-        bf.obest[b] = 1e10f;
-        bf.obestscore[b] = -1;
-        bf.cst[b] = initial_const;
-        bf.lower[b] = 0.0;
-        bf.upper[b] = 1e10;
-    }
+    if (threadIdx.x == 0) search_setup(bf, b, labels, logits, n, initial_const);
     const float* xb = x + b * P;
     for (long long i = threadIdx.x; i < P; i += 256) {
         const float c = clf_clip(xb[i], lo, hi);
@@ -148,25 +93,10 @@ __global__ __launch_bounds__(256) void ead_reset_kernel(EadBufs bf, long long N,
                                                          int repeat_last, int targeted) {
     const long long b = blockIdx.x;
     if (threadIdx.x == 0) {
-        if (update) {
-            const int bs = bf.bestscore[b], t = bf.lab[b];
-            const double c = bf.cst[b];
-            if (bs != -1 && (targeted ? bs == t : bs != t)) {
-                bf.upper[b] = fmin(bf.upper[b], c);
-                if (bf.upper[b] < 1e9) bf.cst[b] = (bf.lower[b] + bf.upper[b]) / 2;
-            } else {
-                bf.lower[b] = fmax(bf.lower[b], c);
-                bf.cst[b] = bf.upper[b] < 1e9 ? (bf.lower[b] + bf.upper[b]) / 2 : c * 10;
-            }
-        }
-        if (!reset) return;
-        if (repeat_last) bf.cst[b] = bf.upper[b];
-        bf.best[b] = 1e10f;
-        bf.bestscore[b] = -1;
-        bf.improved[b] = 0;
-        if (b % batch_size == 0) {
-            bf.prev[b / batch_size] = 1e6;
-            bf.abort_iter[b / batch_size] = -1;
+        if (update) search_update_const(bf, b, targeted);
+        if (reset) {
+            search_reset_scalars(bf, b, batch_size, repeat_last);
+            bf.improved[b] = 0;
         }
     }
     if (!reset) return;
@@ -183,21 +113,15 @@ __global__ __launch_bounds__(64) void ead_slack_head_kernel(const float* __restr
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= N) return;
     float* sd = bf.seed + (long long)b * n;
-    for (int k = 0; k < n; ++k) sd[k] = 0.f;
     const int t = bf.lab[b];
-    if (bf.abort_iter[b / batch_size] >= 0 || t < 0 || t >= n) return;
+    if (bf.abort_iter[b / batch_size] >= 0 || t < 0 || t >= n) {
+        for (int k = 0; k < n; ++k) sd[k] = 0.f;
+        return;
+    }
     const float* z = logits + (long long)b * n;
     float oth;
-    const float arg = ead_hinge_arg(z, n, t, targeted, confidence, &oth);
-    if (!(arg > 0.f)) return;
-    int cnt = 0;
-    for (int k = 0; k < n; ++k) cnt += ((k == t ? -10000.0f : z[k]) == oth) ? 1 : 0;
-    const float c = (float)bf.cst[b];
-    const float sgn = targeted ? -1.0f : 1.0f;
-    const float share = (1.0f / (float)cnt) * (-sgn * c);
-    for (int k = 0; k < n; ++k)
-        if (k != t && z[k] == oth) sd[k] = share;
-    sd[t] = sgn * c;
+    const float arg = cw_hinge_arg(z, n, t, targeted, confidence, &oth);
+    cw_hinge_seed(sd, z, n, t, targeted, (float)bf.cst[b], arg, oth);
 }
 
 // (a) one thread per image, on the iterate's logits: const * loss1_X, success on Z', the first argmax of Z
@@ -207,66 +131,24 @@ __global__ __launch_bounds__(64) void ead_iterate_head_kernel(const float* __res
     if (b >= N || bf.abort_iter[b / batch_size] >= 0) return;
     const float* z = logits + (long long)b * n;
     const int t = bf.lab[b];
-    bf.score[b] = ead_first_argmax(z, n);
+    bf.score[b] = clf_first_argmax(z, n);
     if (t < 0 || t >= n) {                             // a label outside the classes: never a success, no loss
         bf.loss1[b] = 0.f;
         bf.succ[b] = 0;
         return;
     }
     float oth;
-    const float arg = ead_hinge_arg(z, n, t, targeted, confidence, &oth);
+    const float arg = cw_hinge_arg(z, n, t, targeted, confidence, &oth);
     bf.loss1[b] = (float)bf.cst[b] * (arg > 0.f ? arg : 0.f);
-    int am = 0;
-    float best = t == 0 ? (targeted ? z[0] - confidence : z[0] + confidence) : z[0];
-    for (int k = 1; k < n; ++k) {
-        const float zk = k == t ? (targeted ? z[k] - confidence : z[k] + confidence) : z[k];
-        if (zk > best) { best = zk; am = k; }
-    }
-    bf.succ[b] = targeted ? (am == t) : (am != t);
+    bf.succ[b] = cw_success(z, n, t, targeted, confidence);
 }
 
 // (b) one workgroup per chunk: the chunk's loss in a fixed order, the abort decision on check iterations, best tracking by the
 // decision rule's criterion (rule 0: l2 + beta l1, rule 1: l1)
 __global__ __launch_bounds__(256) void ead_chunk_kernel(EadBufs bf, int N, int batch_size, int iter, int check, float beta, int rule) {
-    __shared__ int abort_now, stopped;
-    const int c = blockIdx.x;
-    const int first = c * batch_size;
-    const int cnt = N - first < batch_size ? N - first : batch_size;
-    // thread 0 alone reads and writes the chunk's abort state; the others learn it after the barrier
-    if (threadIdx.x == 0) {
-        stopped = bf.abort_iter[c] >= 0;
-        abort_now = 0;
-        if (!stopped && check) {
-            double L = 0.0;
-            for (int j = 0; j < cnt; ++j)
-                L += ((double)bf.loss1[first + j] + (double)bf.l2[first + j]) + (double)beta * (double)bf.l1[first + j];
-            if (L > bf.prev[c] * 0.9999) {
-                bf.abort_iter[c] = iter;
-                abort_now = 1;
-            } else {
-                bf.prev[c] = L;
-            }
-        }
-    }
-    __syncthreads();
-    if (stopped) return;
-    for (int j = threadIdx.x; j < cnt; j += 256) {
-        const int b = first + j;
-        int imp = 0;
-        if (!abort_now && bf.succ[b]) {
-            const float crit = rule ? bf.l1[b] : __builtin_fmaf(beta, bf.l1[b], bf.l2[b]);
-            if (crit < bf.best[b]) {
-                bf.best[b] = crit;
-                bf.bestscore[b] = bf.score[b];
-            }
-            if (crit < bf.obest[b]) {
-                bf.obest[b] = crit;
-                bf.obestscore[b] = bf.score[b];
-                imp = 1;
-            }
-        }
-        bf.improved[b] = imp;
-    }
+    search_chunk(
+        bf, N, batch_size, iter, check, [&](int b) { return ((double)bf.loss1[b] + (double)bf.l2[b]) + (double)beta * (double)bf.l1[b]; },
+        [&](int b) { return rule ? bf.l1[b] : __builtin_fmaf(beta, bf.l1[b], bf.l2[b]); });
 }
 
 // (d) one workgroup per image: x_adv = X where the image improved (the iterate the chunk kernel just judged), then -- unless
@@ -304,8 +186,8 @@ __global__ __launch_bounds__(256) void ead_update_kernel(EadBufs bf, const float
         s1 += fabsf(e);
         s2 = __builtin_fmaf(e, e, s2);
     }
-    const float t1 = ead_block_sum(s1, red);
-    const float t2 = ead_block_sum(s2, red);
+    const float t1 = clf_block_sum(s1, red);
+    const float t2 = clf_block_sum(s2, red);
     if (threadIdx.x == 0) {
         bf.l1[b] = t1;
         bf.l2[b] = t2;
@@ -313,12 +195,6 @@ __global__ __launch_bounds__(256) void ead_update_kernel(EadBufs bf, const float
 }
 
 }  // namespace
-
-void ead_release(EadWork* w) {
-    if (!w) return;
-    if (w->mem) (void)hipFree(w->mem);
-    delete w;
-}
 
 extern "C" {
 
@@ -342,8 +218,7 @@ int dg_ead(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted
     hipStream_t s = (hipStream_t)stream;
     EadBufs bf;
     const size_t need = carve(&bf, nullptr, N, P, n, chunks);
-    if (!h->ead) h->ead = new EadWork();
-    int rc = clf_grow(&h->ead->mem, 1, h->ead->bytes, need);
+    int rc = search_workspace(&h->ead, need);
     if (rc) return rc;
     carve(&bf, h->ead->mem, N, P, n, chunks);
 
@@ -354,7 +229,7 @@ int dg_ead(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted
                        lo, hi, initial_const, bf, x_adv);
     CLF_TRY(hipGetLastError());
     const unsigned hgrid = (unsigned)((N + 63) / 64);
-    const int every = max_iterations / 10 > 0 ? max_iterations / 10 : 1;
+    const int every = search_every(max_iterations);
     float* const Yrows = bf.xy;
     float* const Xrows = bf.xy + N * P;
     // steps 5-7 of iteration `it` from the logits of its X, which lie `row0` rows into the kept logits
@@ -365,8 +240,8 @@ int dg_ead(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted
                            (abort_early && it % every == 0) ? 1 : 0, beta, decision_rule);
     };
     for (int step = 0; step < binary_search_steps; ++step) {
-        const int repeat_last = (binary_search_steps >= 10 && step == binary_search_steps - 1) ? 1 : 0;
-        hipLaunchKernelGGL(ead_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, N, P, batch_size, step > 0 ? 1 : 0, 1, repeat_last, tg);
+        hipLaunchKernelGGL(ead_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, N, P, batch_size, step > 0 ? 1 : 0, 1,
+                           search_repeat_last(binary_search_steps, step), tg);
         for (int it = 0; it < max_iterations; ++it) {
             if (it == 0) {
                 if ((rc = clf_kept_forward(h, Yrows, B, s))) return rc;
@@ -386,18 +261,11 @@ int dg_ead(dg_clf* h, const float* x, const int32_t* labels, int B, int targeted
         judge(max_iterations - 1, 0);
         hipLaunchKernelGGL(ead_update_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, nullptr, x_adv, N, P, batch_size, 0.f, 0.f, beta, lo, hi, 1);
         CLF_TRY(hipGetLastError());
-        if (chunk_stop)
-            CLF_TRY(hipMemcpyAsync(chunk_stop + (long long)step * chunks, bf.abort_iter, chunks * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        if ((rc = search_copy_chunk_stop(bf, chunk_stop, step, chunks, s))) return rc;
     }
-    if (final_const) {
-        if (binary_search_steps > 0)
-            hipLaunchKernelGGL(ead_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, N, P, batch_size, 1, 0, 0, tg);
-        CLF_TRY(hipGetLastError());
-        CLF_TRY(hipMemcpyAsync(final_const, bf.cst, N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    CLF_TRY(hipMemcpyAsync(best_dist, bf.obest, N * sizeof(float), hipMemcpyDeviceToDevice, s));
-    CLF_TRY(hipMemcpyAsync(best_class, bf.obestscore, N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    return DG_OK;
+    if (final_const && binary_search_steps > 0)          // the last step's constant update alone
+        hipLaunchKernelGGL(ead_reset_kernel, dim3((unsigned)N), dim3(256), 0, s, bf, N, P, batch_size, 1, 0, 0, tg);
+    return search_copy_out(bf, N, final_const, best_dist, best_class, s);
 }
 
 }  // extern "C"

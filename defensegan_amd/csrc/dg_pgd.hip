@@ -17,9 +17,9 @@
 // many images share a call.  No atomics, no host synchronisation, no graph capture.  gfx950 only.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cstdint>
 
+#include "dg_attack_device.h"
 #include "dg_clf_internal.h"
 
 struct PgdWork {
@@ -49,11 +49,9 @@ __global__ __launch_bounds__(256) void pgd_mask_seed_kernel(float* __restrict__ 
 }
 
 // Best tracking for iterate k off the logits its forward kept.  One wave per image (four per workgroup, the waves strided over the
-// images), the classes strided over the 64 lanes: each lane keeps the first maximum of its classes, a butterfly keeps the larger
-// value and, of equal values, the smaller class -- dg_eval_batch's first arg-max.  A NaN logit follows clf_eval_kernel's scan
-// (best = 0; s[k] > s[best] moves it): a NaN is never a candidate, so a lane skips it and a lane that holds nothing but NaNs has no
-// candidate (arg == INT_MAX) for the butterfly to forward; a NaN at class 0 wins every comparison there, as does a row of NaNs, and
-// the answer is class 0.  Then dg_bpda_track's rule: an image without a
+// images), the prediction by clf_wave_class (dg_attack_device.h) -- dg_eval_batch's first arg-max, NaN rules included: a NaN is
+// never a candidate; a NaN at class 0 wins every comparison of clf_eval_kernel's scan, as does a row of NaNs, and the answer is
+// class 0.  Then dg_bpda_track's rule: an image without a
 // success so far (first_success < 0) takes iterate k as its best, and k as its first success where the arg-max is not the label.
 // first_success[b] is read and written by image b's wave alone, the read (one load instruction of the whole wave) before the write.
 __global__ __launch_bounds__(256) void pgd_track_kernel(const float* __restrict__ logits, int n, const int32_t* __restrict__ labels, int B, int k,
@@ -62,20 +60,7 @@ __global__ __launch_bounds__(256) void pgd_track_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (long long b = (long long)blockIdx.x * 4 + wave; b < B; b += (long long)gridDim.x * 4) {
         if (first_success[b] >= 0) continue;                    // uniform over the wave
-        const float* r = logits + b * n;
-        float best = -__builtin_inff();
-        int arg = INT_MAX;
-        for (int c = lane; c < n; c += 64) {
-            const float v = r[c];
-            if (v == v && (arg == INT_MAX || v > best)) { best = v; arg = c; }          // v == v: not a NaN
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const float ob = __shfl_xor(best, m, 64);
-            const int oa = __shfl_xor(arg, m, 64);
-            if (oa != INT_MAX && (arg == INT_MAX || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
-        }
-        if (r[0] != r[0] || arg == INT_MAX) arg = 0;            // uniform over the wave: every lane reads class 0
+        const int arg = clf_wave_class(logits + b * n, n, lane);          // uniform over the wave
         const float* src = x_iter + b * row_elems;
         float* dst = x_best + b * row_elems;
         for (long long i = lane; i < row_elems; i += 64) dst[i] = src[i];
