@@ -87,6 +87,8 @@ SYMBOLS = [
     ("dg_deepfool", _i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     ("dg_deepfool_choices", _i, [_vp, _i, _i, _vp, _vp]),
     ("dg_ead", _i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _f, _i, _i, _i, C.c_double, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dg_jsma", _i, [_vp, _vp, _vp, _i, _f, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("dg_jsma_choices", _i, [_vp, _i, _i, _vp, _vp]),
     ("dg_comm_unique_id", _i, [_vp]),
     ("dg_comm_create", _i, [_i, _vp, _i, _i, C.POINTER(_vp)]),
     ("dg_comm_destroy", _i, [_vp]),

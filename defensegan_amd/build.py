@@ -17,7 +17,7 @@ LIB = os.path.join(LIBDIR, "libdefensegan_hip.so")
 # the same sources with -DDG_MEASURE: in-kernel phase traces, phase-removal switches and the superseded tail kernels kept as
 # cross-checks (tools/, tests/test_gpu_variants.py).  Never loaded by the product path.
 LIB_MEASURE = os.path.join(LIBDIR, "libdefensegan_hip_measure.so")
-SOURCES = ["dg_engine.cpp", "dg_engine_lists.cpp", "dg_engine_prof.cpp", "dg_engine_opts.cpp", "dg_comm.cpp", "dg_plan.cpp", "dg_gemm.hip", "dg_fgemm.hip", "dg_linear.hip", "dg_turn.hip", "dg_tail_mnist.hip", "dg_tail_celeba.hip", "dg_bn.hip", "dg_small.hip", "dg_clf.hip", "dg_cw.hip", "dg_clf_train.hip", "dg_jacobian.hip", "dg_bpda.hip", "dg_pgd.hip", "dg_ball.hip", "dg_spsa.hip", "dg_critic.hip", "dg_gen_train.hip", "dg_latent.hip", "dg_deepfool.hip", "dg_ead.hip"]
+SOURCES = ["dg_engine.cpp", "dg_engine_lists.cpp", "dg_engine_prof.cpp", "dg_engine_opts.cpp", "dg_comm.cpp", "dg_plan.cpp", "dg_gemm.hip", "dg_fgemm.hip", "dg_linear.hip", "dg_turn.hip", "dg_tail_mnist.hip", "dg_tail_celeba.hip", "dg_bn.hip", "dg_small.hip", "dg_clf.hip", "dg_cw.hip", "dg_clf_train.hip", "dg_jacobian.hip", "dg_bpda.hip", "dg_pgd.hip", "dg_ball.hip", "dg_spsa.hip", "dg_critic.hip", "dg_gen_train.hip", "dg_latent.hip", "dg_deepfool.hip", "dg_ead.hip", "dg_jsma.hip"]
 HEADERS = ["dg_clf_internal.h", "dg_attack_device.h", "dg_bsearch.h", "dg_shared_math.h", "dg_engine.h", "dg_gen_internal.h", "dg_kernels.h", "dg_tail_common.h", "dg_device.h", "dg_plan.h", "dg_types.h", "dg_frag_lds.h", "dg_pack.h", os.path.join("..", "..", "include", "defensegan_hip.h")]
 ARCH = "gfx950"
 

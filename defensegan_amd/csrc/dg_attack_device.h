@@ -1,6 +1,6 @@
 // The device arithmetic the attack kernels share, each rule written once so that its users cannot drift apart: the fixed-order
 // sums, the row vector, the first arg-max (by one wave and by one thread) and Carlini-Wagner's hinge.  Included by dg_ball.hip,
-// dg_critic.hip, dg_cw.hip, dg_deepfool.hip, dg_ead.hip, dg_pgd.hip and dg_clf.hip.  Nothing but __device__ __forceinline__
+// dg_critic.hip, dg_cw.hip, dg_deepfool.hip, dg_ead.hip, dg_jsma.hip, dg_pgd.hip and dg_clf.hip.  Nothing but __device__ __forceinline__
 // functions: no state, no kernels, no launch geometry.  The bits of every function here are pinned by the CPU references under
 // tests/support/; changing an order of operations changes results.
 #pragma once

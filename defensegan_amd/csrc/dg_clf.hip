@@ -401,6 +401,7 @@ int dg_clf_destroy(dg_clf* h) {
     critic_release(h->critic);
     deepfool_release(h->deepfool);
     search_release(h->ead);
+    jsma_release(h->jsma);
     delete h;
     return DG_OK;
 }

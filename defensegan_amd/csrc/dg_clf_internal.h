@@ -1,7 +1,8 @@
 // The classifier handle as its source files see it.  Included by: dg_clf.hip (the layers, the evaluation and input-gradient kernels),
 // dg_clf_train.hip (training), dg_jacobian.hip (class gradients, Jacobian augmentation), dg_bpda.hip (the BPDA/EOT step), dg_pgd.hip
 // (PGD on the bare classifier), dg_ball.hip (the per-image norms and steps of the L1 / L2 attacks), dg_spsa.hip (SPSA), dg_latent.hip
-// (the latent-space attack), dg_critic.hip (the WGAN-GP critic's cost, gradient and step), dg_deepfool.hip (the DeepFool loop) and,
+// (the latent-space attack), dg_critic.hip (the WGAN-GP critic's cost, gradient and step), dg_deepfool.hip (the DeepFool loop), dg_jsma.hip (the saliency-map
+// attack) and,
 // through dg_bsearch.h, dg_cw.hip (the Carlini-Wagner attack) and dg_ead.hip (the elastic-net attack).  Everything here is internal
 // to the library: plain C++ under hidden visibility, nothing of it is exported.
 #pragma once
@@ -42,6 +43,7 @@ struct BpdaWork;     // dg_bpda.hip
 struct PgdWork;      // dg_pgd.hip
 struct CriticWork;   // dg_critic.hip
 struct DeepfoolWork; // dg_deepfool.hip
+struct JsmaWork;     // dg_jsma.hip
 
 struct dg_clf {
     int device = 0;
@@ -70,6 +72,7 @@ struct dg_clf {
     CriticWork* critic = nullptr;             // the WGAN-GP critic's three-batch workspace, grown on demand
     DeepfoolWork* deepfool = nullptr;         // DeepFool's candidates, seeds, iterate rows and per-image state, grown on demand
     SearchWork* ead = nullptr;               // the elastic-net attack's slack / iterate rows and per-image state, grown on demand
+    JsmaWork* jsma = nullptr;                 // the saliency-map attack's doubled iterate rows, seeds, domain and per-image state, grown on demand
 
     int pixels() const { return in_h * in_w * in_c; }
 };
@@ -122,6 +125,7 @@ void bpda_release(BpdaWork* w);      // dg_bpda.hip
 void pgd_release(PgdWork* w);        // dg_pgd.hip
 void critic_release(CriticWork* w);  // dg_critic.hip
 void deepfool_release(DeepfoolWork* w);   // dg_deepfool.hip
+void jsma_release(JsmaWork* w);      // dg_jsma.hip
 
 // ---- dg_clf_train.hip -------------------------------------------------------------------------------------------------------------
 // How a Conv2D / Linear layer's weight gradient over B images is cut: `slots` runs of kc terms of its reduction axis, each slot
@@ -139,7 +143,7 @@ void train_launch_wgrad(const ClfLayer& v, const float* x, const float* g, const
 // and the step count.  Fetch them per call: adding a layer moves them.
 int train_adam_state(dg_clf* h, float*** m, float*** v, long long** t);
 
-// ---- shared by the attack steps (dg_bpda.hip, dg_ball.hip, dg_spsa.hip, dg_deepfool.hip, dg_ead.hip; dg_attack_device.h has the reductions) ----
+// ---- shared by the attack steps (dg_bpda.hip, dg_ball.hip, dg_spsa.hip, dg_deepfool.hip, dg_ead.hip, dg_jsma.hip; dg_attack_device.h has the reductions) ----
 // the final clip of every attack step: clip(v, lo, hi) with lo <= hi
 __device__ __forceinline__ float clf_clip(float v, float lo, float hi) {
     v = v < lo ? lo : v;

@@ -2,8 +2,8 @@
 device:
 
     whitebox    trains the classifier (cleverhans model_train; ``adv_tr`` adds FGSM inputs; ``train_on_recs`` trains on cached
-                reconstructions), attacks the ORIGINAL test images (fgsm, rand_fgsm, cw -- and pgd on a bare model, bpda and latent
-                on a defended one, spsa on either, which the reference has not) and measures the accuracy on the adversarial images, through the
+                reconstructions), attacks the ORIGINAL test images (fgsm, rand_fgsm, cw -- and pgd and jsma on a bare model, bpda and
+                latent on a defended one, spsa on either, which the reference has not) and measures the accuracy on the adversarial images, through the
                 Defense-GAN projection for ``defense_gan`` (with the ROC triple)                       whitebox.py:56-233
     main        the flags and the result files of whitebox.py:236-392
 
@@ -15,6 +15,7 @@ device:
     python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --init_path output/gans/mnist \\
         --defense_type defense_gan --attack_type spsa --spsa_samples 32 --spsa_delta 0.01 --num_tests 100
     python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --defense_type none --attack_type ead --ead_beta 1e-2 --ead_rule L1
+    python -m defensegan_amd.whitebox --cfg mnist --data_dir data/mnist --defense_type none --attack_type jsma --jsma_theta 1.0 --jsma_gamma 0.1
 
 Kept from the reference: ``RandomState([11, 24, 1990])`` for the training schedule; the clean accuracy on the (reconstructed) test
 split printed after every epoch; with ``defense_gan`` the reconstruction layer is attached AFTER training and BEFORE the attack
@@ -30,7 +31,7 @@ import numpy as np
 from . import config, datasets, gan_defense, network_builder, py2pickle, utils_tf
 from .blackbox import SEED, _Phase, _accuracy, _labels, load_recs, result_path
 
-ATTACKS = ("fgsm", "cw", "pgd", "bpda", "latent", "spsa", "ead")
+ATTACKS = ("fgsm", "cw", "pgd", "bpda", "latent", "spsa", "ead", "jsma")
 # whitebox.py:203-209; 'feed' is TensorFlow's business
 CW_PARAMS = {"binary_search_steps": 1, "max_iterations": 100, "learning_rate": 10.0, "initial_const": 100}
 # the elastic-net attack (network_builder.ElasticNetMethod): this setting is chosen here, not taken from the reference, which has no ead
@@ -41,6 +42,9 @@ ITERATIVE_DEFAULTS = {"eps_iter": 0.05, "nb_iter": 10, "eot_samples": 1}
 LATENT_DEFAULTS = {"latent_iters": 100, "latent_lr": 0.05, "latent_c": 1.0}
 # the score-based black-box attack (network_builder.SPSA): direction pairs per iteration and the probe size; eps_iter and nb_iter as pgd's
 SPSA_DEFAULTS = {"spsa_samples": 32, "spsa_delta": 0.01}
+# the saliency-map attack (network_builder.SaliencyMapMethod): the step per feature and the share of the features it may move; chosen
+# here, the reference has no jsma (cleverhans' own default is gamma 1.0: every feature)
+JSMA_DEFAULTS = {"jsma_theta": 1.0, "jsma_gamma": 0.1}
 PGD_CALL_IMAGES = 10000                       # images per dg_pgd call: bounds the kept activations, not the result
 
 
@@ -54,26 +58,26 @@ def attack_kind(attack_type):
     if "fgsm" in t:
         return "fgsm", rand
     base = t.replace("rand", "").strip("_+")
-    if base in ATTACKS and not (rand and base in ("cw", "latent", "spsa", "ead")):
+    if base in ATTACKS and not (rand and base in ("cw", "latent", "spsa", "ead", "jsma")):
         return base, rand
-    raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, ead, pgd (defense_type none / adv_tr), bpda or latent (defense_gan), spsa" % (attack_type,))
+    raise ValueError("unknown attack_type %r: fgsm, rand_fgsm, cw, ead, pgd or jsma (defense_type none / adv_tr), bpda or latent (defense_gan), spsa" % (attack_type,))
 
 
 def attack_ord_value(attack_ord, kind=None):
     """``attack_ord`` (np.inf, 1, 2 or their names 'inf', '1', '2') as np.inf or an int, checked against the attack ``kind``: fgsm
     takes 1 and 2 (``FastGradientMethod``'s ord), pgd and bpda take 2 (1 is NotImplementedError: the L1 projection needs a sort), cw
-    is an L2 attack already and takes none, as do latent and spsa; ead is the L1 attack and takes none either."""
+    is an L2 attack already and takes none, as do latent and spsa; ead is the L1 attack and jsma the L0 attack, and they take none either."""
     who = "attack_ord" if kind is None else "attack_ord with attack_type %s" % kind
-    allowed = {"fgsm": (np.inf, 1, 2), "pgd": (np.inf, 2), "bpda": (np.inf, 2), "cw": (np.inf,), "ead": (np.inf,), "latent": (np.inf,), "spsa": (np.inf,)}.get(kind, (np.inf, 1, 2))
+    allowed = {"fgsm": (np.inf, 1, 2), "pgd": (np.inf, 2), "bpda": (np.inf, 2), "cw": (np.inf,), "ead": (np.inf,), "latent": (np.inf,), "spsa": (np.inf,), "jsma": (np.inf,)}.get(kind, (np.inf, 1, 2))
     return network_builder._attack_ord(attack_ord, allowed, who)
 
 
 def _attack_params(kind, attack_params):
     """The overrides ``attack_params`` holds for this attack: eps_iter / nb_iter (pgd, bpda), eot_samples (bpda), any
-    CarliniWagnerL2 parameter (cw), latent_iters / latent_lr / latent_c (latent), eps_iter / nb_iter / spsa_samples / spsa_delta (spsa), ead_beta / ead_rule and any ElasticNetMethod parameter (ead).  Values of None and the iterative attacks' keys given to another attack are left out."""
+    CarliniWagnerL2 parameter (cw), latent_iters / latent_lr / latent_c (latent), eps_iter / nb_iter / spsa_samples / spsa_delta (spsa), ead_beta / ead_rule and any ElasticNetMethod parameter (ead), jsma_theta / jsma_gamma (jsma).  Values of None and the iterative attacks' keys given to another attack are left out."""
     given = {k: v for k, v in (attack_params or {}).items() if v is not None}
     known = (set(ITERATIVE_DEFAULTS) | set(network_builder.CarliniWagnerL2.DEFAULTS) | set(LATENT_DEFAULTS) | set(SPSA_DEFAULTS)
-             | set(EAD_DEFAULTS) | set(network_builder.ElasticNetMethod.DEFAULTS))
+             | set(EAD_DEFAULTS) | set(network_builder.ElasticNetMethod.DEFAULTS) | set(JSMA_DEFAULTS))
     if set(given) - known:
         raise ValueError("unknown attack_params: %s" % sorted(set(given) - known))
     if kind == "cw":
@@ -85,6 +89,8 @@ def _attack_params(kind, attack_params):
         return out
     if kind == "latent":
         return {k: given.get(k, d) for k, d in LATENT_DEFAULTS.items()}
+    if kind == "jsma":
+        return {k: given.get(k, d) for k, d in JSMA_DEFAULTS.items()}
     keys = {"pgd": ("eps_iter", "nb_iter"), "bpda": ("eps_iter", "nb_iter", "eot_samples"), "spsa": ("eps_iter", "nb_iter")}.get(kind, ())
     out = {k: given.get(k, ITERATIVE_DEFAULTS[k]) for k in keys}
     if kind == "spsa":
@@ -116,6 +122,11 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
                         ('EN') and any ElasticNetMethod parameter.  ``norms``: a dict that receives 'l1' and 'l2', the means of
                         ||x_adv - x||_1 and ||x_adv - x||_2 over the images the attack succeeded on (NaN when on none), and 'successes'
       pgd               ProjectedGradientDescent on the true labels: 'none' and 'adv_tr' only
+      jsma              SaliencyMapMethod (the L0 attack), 'none' and 'adv_tr' only; the target of image i is (y_i + 1 + r_i) % nb_classes,
+                        r_i drawn from the training ``RandomState`` (``jsma_targets``): never the true class.  ``attack_params``
+                        jsma_theta (1.0) and jsma_gamma (0.1) -- chosen here, the reference has no jsma.  ``norms``: a dict that
+                        receives 'success_rate' (the share of images whose class at x_adv is the target) and 'l0' (the mean of
+                        n_changed / F over those images, NaN when there is none)
       bpda              BPDA on the true labels: 'defense_gan' only
       latent            LatentAttack on the true labels, ``gan.rec_rr`` restarts per image: 'defense_gan' only.  x_adv = G(z) lies in
                         the generator's range, not in the ``eps`` ball; ``attack_params`` latent_iters (100), latent_lr (0.05), latent_c (1)
@@ -150,6 +161,9 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
         if kind[0] == "pgd" and defended:
             raise ValueError("attack_type pgd differentiates a bare classifier (defense_type none or adv_tr); with defense_gan the "
                              "iterative attack is bpda")
+        if kind[0] == "jsma" and defended:
+            raise ValueError("attack_type jsma differentiates a bare classifier (defense_type none or adv_tr): the gradient through the "
+                             "projection is zero and no pair of features is admissible")
         if kind[0] == "bpda" and not defended:
             raise ValueError("attack_type bpda needs the projection (defense_type defense_gan); on a bare classifier (%s) the "
                              "iterative attack is pgd" % defense_type)
@@ -234,6 +248,17 @@ def whitebox(gan, model, data, rec_data_path=None, batch_size=128, learning_rate
             attack = network_builder.ProjectedGradientDescent(model)
             x_adv = attack.generate(test_adv_from, test_labels, eps=eps, clip_min=min_val, clip_max=1.0, seed=seed,
                                     batch_size=PGD_CALL_IMAGES, **extra)
+        elif kind == "jsma":
+            attack = network_builder.SaliencyMapMethod(model)
+            y_target = jsma_targets(test_labels, int(model.nb_classes), rng)
+            x_adv, _, jsma_class, jsma_changed = attack.generate(test_adv_from, y_target=y_target, theta=float(extra["jsma_theta"]),
+                                                                 gamma=float(extra["jsma_gamma"]), clip_min=min_val, clip_max=1.0,
+                                                                 return_info=True)
+            summary = jsma_summary(jsma_class, y_target, jsma_changed, int(np.prod(np.asarray(test_adv_from).shape[1:])))
+            if norms is not None:
+                norms.update(summary)
+            print("[*] jsma: success rate %0.4f, mean share of features changed on the successful images %0.4f" %
+                  (summary["success_rate"], summary["l0"]))
         elif kind == "latent":
             attack = network_builder.LatentAttack(model, gan)
             x_adv = attack.generate(test_adv_from, test_labels, rec_rr=int(gan.rec_rr), nb_iter=int(extra["latent_iters"]),
@@ -271,6 +296,24 @@ def ead_norms(x_adv, x, best_class, dev):
     return out
 
 
+def jsma_targets(labels, nb_classes, rng):
+    """The target class per image of ``--attack_type jsma``: ``(y + 1 + r) % nb_classes`` with ``r = rng.randint(0, nb_classes - 1, n)``,
+    one draw for all images: uniform over the classes that are not the true one."""
+    y = np.asarray(labels).astype(np.int64)
+    if int(nb_classes) < 2:
+        raise ValueError("jsma needs at least 2 classes to draw a target from")
+    r = rng.randint(0, int(nb_classes) - 1, len(y))
+    return ((y + 1 + r) % int(nb_classes)).astype(np.int32)
+
+
+def jsma_summary(final_class, y_target, n_changed, features):
+    """{'success_rate', 'l0'}: the share of images with ``final_class == y_target`` and the mean of ``n_changed / features`` over them
+    (float64 on the host; NaN when none succeeded)."""
+    ok = np.asarray(final_class) == np.asarray(y_target)
+    l0 = np.asarray(n_changed, np.float64)[ok] / float(features)
+    return {"success_rate": float(ok.mean()) if ok.size else float("nan"), "l0": float(l0.mean()) if ok.any() else float("nan")}
+
+
 # ---------------------------------------------------------------------------------------------------- result files, CLI
 def get_results_dir_filename(flags, gan):
     """whitebox.py:309-341 ``_get_results_dir_filename``: (results directory, file name without the counter prefix).
@@ -301,12 +344,15 @@ def get_results_dir_filename(flags, gan):
 
 def write_results(path, accuracies, norms=None):
     """whitebox.py:295-306: the line ``str(acc) + ' ' + '0 '`` (appended) and, with roc_info, ``*_roc.pkl`` in a pickle the
-    Python-2 reference reads.  ``norms`` (ead: whitebox()'s dict) adds two entries to the line: ``l1=<mean> l2=<mean>``."""
+    Python-2 reference reads.  ``norms`` (whitebox()'s dict) adds two entries to the line: ``l1=<mean> l2=<mean>`` for ead,
+    ``success=<rate> l0=<mean share of features changed on the successful images>`` for jsma."""
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with open(path, "a") as f:
         f.writelines([str(accuracies[i]) + " " for i in range(2)])
-        if norms:
+        if norms and "l1" in norms:
             f.write("l1=%s l2=%s " % (norms["l1"], norms["l2"]))
+        if norms and "success_rate" in norms:
+            f.write("success=%s l0=%s " % (norms["success_rate"], norms["l0"]))
         f.write("\n")
     print("[*] saved accuracy in {}".format(path))
     if accuracies[2]:
@@ -333,7 +379,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--random_test_iter", type=int, default=-1, help="accepted and ignored, as in the reference")
     ap.add_argument("--online_training", action="store_true", help="not implemented (NotImplementedError)")
     ap.add_argument("--defense_type", default="none", choices=["none", "defense_gan", "adv_tr"], help="Type of defense")
-    ap.add_argument("--attack_type", default="none", help="Type of attack [fgsm|cw|ead|rand_fgsm|pgd|bpda|latent|spsa]; none: train and stop")
+    ap.add_argument("--attack_type", default="none", help="Type of attack [fgsm|cw|ead|rand_fgsm|pgd|jsma|bpda|latent|spsa]; none: train and stop")
     ap.add_argument("--results_dir", default=None, help="The final subdirectory of the results.")
     ap.add_argument("--model", default="F", choices=sorted(network_builder.MODELS), help="The classifier model.")
     ap.add_argument("--debug_dir", default="temp", help="accepted and ignored (the reference's qualitative debug output)")
@@ -351,6 +397,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--ead_beta", type=float, default=EAD_DEFAULTS["ead_beta"], help="ead: weight of the L1 term (default 1e-3)")
     ap.add_argument("--ead_rule", default=EAD_DEFAULTS["ead_rule"], choices=["EN", "L1"],
                     help="ead: the best iterate is the successful one of the smallest elastic-net (EN) or L1 distance (default EN)")
+    ap.add_argument("--jsma_theta", type=float, default=JSMA_DEFAULTS["jsma_theta"], help="jsma: what a chosen feature moves by (default 1.0; negative: downwards)")
+    ap.add_argument("--jsma_gamma", type=float, default=JSMA_DEFAULTS["jsma_gamma"], help="jsma: the share of the features the attack may move (default 0.1)")
     ap.add_argument("--attack_ord", default="inf", choices=["inf", "1", "2"],
                     help="norm of the attack's ball: pgd / bpda take inf or 2, fgsm / rand_fgsm inf, 1 or 2 (default inf)")
     ap.add_argument("--seed", type=int, default=SEED, help="seed of the Dropout masks and the latent draws")
@@ -402,7 +450,8 @@ def main(argv=None) -> int:
                           attack_params={"eps_iter": args.eps_iter, "nb_iter": args.nb_iter, "eot_samples": args.eot_samples,
                                          "latent_iters": args.latent_iters, "latent_lr": args.latent_lr, "latent_c": args.latent_c,
                                          "spsa_samples": args.spsa_samples, "spsa_delta": args.spsa_delta,
-                                         "ead_beta": args.ead_beta, "ead_rule": args.ead_rule},
+                                         "ead_beta": args.ead_beta, "ead_rule": args.ead_rule,
+                                         "jsma_theta": args.jsma_theta, "jsma_gamma": args.jsma_gamma},
                           seed=args.seed, init_seed=args.init_seed, attack_ord=args.attack_ord, norms=norms)
     write_results(path, accuracies, norms)
     return 0

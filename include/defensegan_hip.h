@@ -598,6 +598,36 @@ int dg_deepfool(dg_clf* h, const float* x, int B, int nb_candidate, float oversh
 int dg_deepfool_choices(dg_clf* h, int B, int max_iter, int32_t* choices, void* stream);
 
 /*
+ * The Jacobian saliency-map attack (Papernot et al. 2016; cleverhans' SaliencyMapMethod; no reference counterpart): the L0 attack of
+ * the suite, targeted, the whole loop enqueued by this one call (defensegan_amd/csrc/dg_jsma.hip's header comment and DESIGN.md
+ * section 7, "Saliency map", give the definition; attacks.SaliencyMapMethod).  x [B,H,W,C], F = H W C features; target [B] int32, the
+ * class each image is to be given (outside [0, classes): the image is left alone).  adv = x; the search domain of an image is its
+ * features with x < clip_max (theta > 0) or x > clip_min (theta < 0).  An iteration of an active image: O = the logits, or with
+ * of_probs = 1 softmax(logits); the image becomes inactive when the first arg-max of O is its target, when O holds a NaN or when fewer
+ * than 2 features are left in its domain; a = grad O[t], b = grad sum_{j != t} O[j] (two seeded backwards; with of_probs = 1, b = -a
+ * up to rounding); over the pairs p < q of the domain, A = a_p + a_q, Bs = b_p + b_q, admissible where A > 0 and Bs < 0 (theta < 0:
+ * A < 0 and Bs > 0), the admissible pair of the largest score -(A Bs) > 0 is taken, ties to the smallest p, then the smallest q, a
+ * NaN score never; without such a pair the image becomes inactive and keeps adv; otherwise adv[p] = clip(adv[p] + theta, clip_min,
+ * clip_max), the same for q, and both leave the domain.  After max_iters iterations, or when no image is active:
+ *   x_adv       [B,H,W,C] adv (required; may be x)
+ *   iters       [B] int32, the pairs the image moved                                              (may be NULL)
+ *   final_class [B] int32, the first arg-max of the logits at x_adv (one more forward); a NaN is never a candidate, class 0 where
+ *               class 0 is a NaN or nothing else is left                                          (may be NULL)
+ *   n_changed   [B] int32, the elements with x_adv != x (a NaN element of x is not counted)       (may be NULL)
+ * max_iters = 0 returns x_adv = x.  DG_E_INVALID: null h, x, target or x_adv, B < 1, theta zero or not finite, max_iters < 0,
+ * clip_min > clip_max, of_probs not 0 or 1, F < 2, F above 5120 ("not implemented for more than"), 2 B max_iters above 2^31 - 1;
+ * DG_E_STATE: incomplete weights.  Device pointers; asynchronous on `stream` except that every second iteration the count of active
+ * images is read back and the loop ends when it is zero, which changes no bit of the result; no graph capture, no float atomics:
+ * a call repeated returns the same bits and an image's result does not depend on which other images share the call.  The workspace
+ * grows on demand (two rows per image through the classifier, one byte per feature).
+ */
+int dg_jsma(dg_clf* h, const float* x, const int32_t* target, int B, float theta, int max_iters, float clip_min, float clip_max,
+            int of_probs, float* x_adv, int32_t* iters, int32_t* final_class, int32_t* n_changed, void* stream);
+/* choices [max_iters, B, 2] int32 (device): the (p, q) of every step of the handle's LAST dg_jsma call, -1 where the image took none
+ * (inactive, no admissible pair, or an iteration the early exit skipped); DG_E_STATE unless that call had this B and max_iters (>= 1). */
+int dg_jsma_choices(dg_clf* h, int B, int max_iters, int32_t* choices, void* stream);
+
+/*
  * The elastic-net attack (Chen et al. 2018, EAD; cleverhans' ElasticNetMethod; no reference counterpart): Carlini-Wagner's loss plus
  * beta * ||x_adv - x0||_1, minimised by iterative shrinkage-thresholding, with `fista` by FISTA; the L1 attack of the suite
  * (defensegan_amd/csrc/dg_ead.hip's header comment and DESIGN.md section 7, "Elastic net", give the algorithm;
