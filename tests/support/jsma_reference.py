@@ -286,3 +286,223 @@ CAP_SOURCES = (("dg_jsma.hip", "unsigned jsma_wave_grid(int B) { return (unsigne
                ("dg_jsma.hip", "constexpr int JSMA_MAX_FEATURES = 5120;"))
 TILE_B = IMAGE_CAP + 2
 TILE_CASE = _case("lin5", (4, 4, 1), 67, of_probs=0, clf_seed=11, x_seed=2, max_iters=2)
+
+
+# ---- the edge cases (tests/test_gpu_jsma_edges.py on the device, tests/test_jsma_edges_cpu.py for what each set was chosen for) ------
+def sparse_images(B, shape, seed, lo=0.0, hi=1.0):
+    """[B, H, W, C] float32, MNIST-like: per element, with u ~ U[0, 1) and then v ~ U[lo, hi) from RandomState(seed), lo where u < 0.45,
+    hi where 0.45 <= u < 0.6, otherwise v.  theta > 0 finds about 85 % of the features in the search domain, theta < 0 about 55 %."""
+    rs = np.random.RandomState(seed)
+    u = rs.uniform(0.0, 1.0, (B,) + tuple(shape))
+    v = rs.uniform(lo, hi, (B,) + tuple(shape))
+    return np.where(u < 0.45, lo, np.where(u < 0.6, hi, v)).astype(np.float32)
+
+
+def conv_model(shape):
+    """Conv2D(8, 3 x 3, stride 1, SAME) + ReLU + Flatten + Linear(10) + Softmax: the model of the channel cases."""
+    from defensegan_amd import network_builder as nb
+    return nb.MLP([nb.Conv2D(8, (3, 3), (1, 1), "SAME"), nb.ReLU(), nb.Flatten(), nb.Linear(10), nb.Softmax()], input_shape=(None,) + tuple(shape))
+
+
+def pair_chunk(F):
+    """The features per thread of jsma_pair_kernel's compaction when x is 16-byte aligned: ceil(F / 256) rounded up to the vector width."""
+    V = 4 if F % 4 == 0 else 1
+    return -(-(-(-F // 256)) // V) * V
+
+
+TIE_BIAS = 1.0e5                     # class 0's bias in the linear tie models: no image reaches its target (the CPU test has the margin)
+TIE_ITERS = 6
+TIE_SHAPES = {16: (4, 4, 1), 25: (5, 5, 1), 784: (28, 28, 1), 1025: (25, 41, 1), 1300: (26, 50, 1), 3072: (32, 32, 3), 5120: (64, 80, 1)}
+TIE_CHUNKS = {16: 4, 25: 1, 784: 4, 1025: 5, 1300: 8, 3072: 12, 5120: 20}
+TIE_THETAS = (1.0, -0.5)
+TIE_PATTERNS = ("full", "last_two", "first_and_last", "three", "every_third", "wave0_empty", "odd_threads", "thirteen")
+
+
+def tie_domains(F):
+    """The domain patterns of the all-ties family, in TIE_PATTERNS' order: sorted index arrays.  'wave0_empty' leaves out everything
+    threads 0 .. 63 of the pair kernel own (nothing is left at F <= 64 chunk: that image takes no step), 'odd_threads' keeps the chunks
+    of the odd threads."""
+    c, idx = pair_chunk(F), np.arange(F)
+    return [idx, idx[-2:], idx[[0, F - 1]], idx[[1, F // 2, F - 2]], idx[::3], idx[idx >= 64 * c], idx[(idx // c) % 2 == 1],
+            np.unique(np.linspace(0, F - 1, 13).astype(np.int64))]
+
+
+def tie_case(F, theta, lo=0.0, hi=1.0):
+    """(model, params, x [8, H, W, C], target, doms) of the all-ties family: two classes, the target's column sign(theta) everywhere and
+    the other column -sign(theta), so a = sign(theta), b = -sign(theta) and every pair in the domain is admissible at score 4.0; a
+    feature in the domain starts a quarter of the range inside it, one outside at the bound that excludes it."""
+    m = model_of("lin2", TIE_SHAPES[F])
+    s = 1.0 if theta > 0 else -1.0
+    W = np.stack([np.full(F, -s), np.full(F, s)], axis=1).astype(np.float32)
+    doms = tie_domains(F)
+    x = np.full((len(doms), F), hi if theta > 0 else lo, np.float32)
+    for i, d in enumerate(doms):
+        x[i, d] = lo + 0.25 * (hi - lo) if theta > 0 else hi - 0.25 * (hi - lo)
+    return m, [(W, np.array([TIE_BIAS, 0.0], np.float32))], x.reshape((len(doms),) + TIE_SHAPES[F]), np.ones(len(doms), np.int32), doms
+
+
+def tie_expected(x, doms, theta, max_iters, lo=0.0, hi=1.0):
+    """What the all-ties family must give, from the patterns alone: step k of image i moves (d[2k], d[2k + 1]) of its sorted domain."""
+    B = len(doms)
+    xa = x.reshape(B, -1).copy()
+    choices = np.full((max_iters, B, 2), -1, np.int32)
+    iters = np.zeros(B, np.int32)
+    for i, d in enumerate(doms):
+        iters[i] = min(max_iters, len(d) // 2)
+        for k in range(iters[i]):
+            choices[k, i] = d[2 * k:2 * k + 2]
+        moved = d[:2 * iters[i]]
+        xa[i, moved] = np.clip(xa[i, moved] + np.float32(theta), np.float32(lo), np.float32(hi))
+    return {"x_adv": xa.reshape(x.shape), "iters": iters, "n_changed": 2 * iters, "final_class": np.zeros(B, np.int32), "choices": choices}
+
+
+# the dyadic family: weights k / 8, |k| <= DYADIC_K <= 16, so every sum and product of the pair rule is exact in float32 and float64
+DYADIC_K = 2
+DYADIC_SHAPES = {25: (5, 5, 1), 784: (28, 28, 1), 1300: (26, 50, 1)}
+DYADIC_ITERS = 8
+DYADIC_CASES = [(F, n, theta) for F in sorted(DYADIC_SHAPES) for n in (2, 3) for theta in (1.0, -1.0, 0.25)]
+
+
+def dyadic_case(F, n, theta, B=6, lo=0.0, hi=1.0):
+    """(model, params, x, target): a linear model of dyadic weights with class 0's bias TIE_BIAS, targets among the other classes, half
+    of every image outside the search domain at random positions.  The weights are k / 8, k uniform in [-DYADIC_K, DYADIC_K].  At F = 25
+    that draw leaves few ties among a dozen features, so there every row is one of three types, (a, b) = (2, 0), (0, -2) or (1, -1)
+    eighths times sign(theta) for target 1: the best pairs, at score 4 / 64, are one of the first with one of the second type or two
+    of the third -- no product set, so "the smallest p, then q" and "the smallest q, then p" name different pairs."""
+    rs = np.random.RandomState(1000 * n + F + (7 if theta < 0 else 0))
+    if F == 25:
+        ab = np.array([(2, 0), (0, -2), (1, -1)])[rs.randint(0, 3, F)] * (1 if theta > 0 else -1)
+        W = np.zeros((F, n))
+        W[:, 1] = ab[:, 0]
+        if n == 3:
+            W[:, 2] = rs.randint(-1, 2, F)
+        W[:, 0] = ab[:, 1] - W[:, 2:].sum(axis=1)
+        W = (W / 8.0).astype(np.float32)
+    else:
+        W = (rs.randint(-DYADIC_K, DYADIC_K + 1, (F, n)) / 8.0).astype(np.float32)
+    b = np.zeros(n, np.float32)
+    b[0] = TIE_BIAS
+    x = images(B, DYADIC_SHAPES[F], int(rs.randint(1 << 30))).reshape(B, F)
+    x[rs.uniform(0.0, 1.0, (B, F)) < 0.5] = hi if theta > 0 else lo
+    t = rs.randint(1, n, B).astype(np.int32)
+    return model_of("lin%d" % n, DYADIC_SHAPES[F]), [(W, b)], x.reshape((B,) + DYADIC_SHAPES[F]), np.ones_like(t) if F == 25 else t
+
+
+def dyadic_run(F, n, theta):
+    """The float64 run of a dyadic case, computed once and shared (never modified).  No shadow: nothing in it rounds."""
+    if ("dyadic", F, n, theta) not in _RUNS:
+        m, p, x, t = dyadic_case(F, n, theta)
+        _RUNS[("dyadic", F, n, theta)] = run(m, p, x, t, theta, DYADIC_ITERS, 0.0, 1.0, False)
+    return _RUNS[("dyadic", F, n, theta)]
+
+
+def linear_margins(params, x, target, choices, theta, lo=0.0, hi=1.0):
+    """[iterations taken + 1, B] float64: logit 0 minus the largest other logit of a linear model at x and after every step of
+    ``choices`` replayed in float64 (rows past the last step of an image repeat its last value)."""
+    W, b = np.asarray(params[0][0], np.float64), np.asarray(params[0][1], np.float64)
+    adv = np.asarray(x, np.float64).reshape(len(x), -1).copy()
+    out = []
+    for k in range(len(choices) + 1):
+        z = adv @ W + b
+        out.append(z[:, 0] - z[:, 1:].max(axis=1))
+        if k < len(choices):
+            for i in np.flatnonzero(choices[k][:, 0] >= 0):
+                pq = choices[k][i]
+                adv[i, pq] = np.clip(adv[i, pq] + theta, lo, hi)
+    return np.array(out)
+
+
+def replay(x, choices, theta, lo, hi):
+    """x with the features of ``choices`` [iters, B, 2] moved in float32, one add and one clip each: what x_adv must be, bit for bit."""
+    xa = np.array(x, np.float32).reshape(len(x), -1)
+    for k in range(len(choices)):
+        for i in np.flatnonzero(choices[k][:, 0] >= 0):
+            pq = choices[k][i]
+            xa[i, pq] = np.clip(xa[i, pq] + np.float32(theta), np.float32(lo), np.float32(hi))
+    return xa.reshape(np.shape(x))
+
+
+def _edge(model, shape, B, clf_seed, x_seed, t_seed, theta, max_iters, of_probs, lo=0.0, hi=1.0, sparse=True, outside=False):
+    return dict(model=model, shape=shape, B=B, clf_seed=clf_seed, x_seed=x_seed, t_seed=t_seed, theta=theta, max_iters=max_iters,
+                of_probs=of_probs, lo=lo, hi=hi, sparse=sparse, outside=outside)
+
+
+INF = float("inf")
+OUTSIDE_SEEDS = (29, 30)             # clf and x seed of the two images that start outside [0, 1]
+EDGE_CASES = {}
+for _th in (1.0, -1.0, 0.5):         # 2. sparse domains on the two-layer model, 28 x 28
+    for _pr in (0, 1):
+        EDGE_CASES["sparse_th%g_p%d" % (_th, _pr)] = _edge("mlp10", (28, 28, 1), 8, 7, 21, 22, _th, 20, _pr)
+for _th in (0.5, -0.5):              # 3. clip ranges, 5 x 6
+    EDGE_CASES["signed_th%g" % _th] = _edge("mlp10", (5, 6, 1), 16, 7, 23, 24, _th, 15, 0, -1.0, 1.0)
+    EDGE_CASES["unbounded_th%g" % _th] = _edge("mlp10", (5, 6, 1), 16, 7, 23, 24, _th, 15, 0, -INF, INF)
+    EDGE_CASES["point_th%g" % _th] = _edge("mlp10", (5, 6, 1), 16, 7, 23, 24, _th, 15, 0, 0.5, 0.5)
+    EDGE_CASES["outside_th%g" % _th] = _edge("mlp10", (5, 6, 1), 2, OUTSIDE_SEEDS[0], OUTSIDE_SEEDS[1], 24, _th, 15, 0, 0.0, 1.0, outside=True)
+for _sh in ((6, 5, 3), (4, 6, 3)):   # 4. channels and non-square images: gamma 0.5
+    for _pr in (0, 1):
+        EDGE_CASES["conv%dx%dx%d_p%d" % (_sh + (_pr,))] = _edge("conv8", _sh, 12, 9, 25, 26, 1.0, int(np.prod(_sh)) // 4, _pr, sparse=False)
+for _pr in (0, 1):                   # 5. many classes: four trips of the 64 lanes
+    EDGE_CASES["mlp200_p%d" % _pr] = _edge("mlp200", (5, 5, 1), 6, 5, 27, 28, 1.0, 6, _pr, sparse=False)
+SPARSE_CASES = sorted(k for k in EDGE_CASES if k.startswith("sparse"))
+RANGE_CASES = sorted(k for k in EDGE_CASES if k[:5] in ("signe", "unbou", "point", "outsi"))
+CONV_CASES = sorted(k for k in EDGE_CASES if k.startswith("conv"))
+MANY_CLASS_CASES = sorted(k for k in EDGE_CASES if k.startswith("mlp200"))
+
+
+def edge_inputs(name):
+    """(model, params, x, target) of an EDGE_CASES entry (no device touched).  The images that start outside the range: elements 3,
+    11 and 20 of image 0 and 5, 17 and 26 of image 1 are 1.5, -0.5, 1.5."""
+    c = EDGE_CASES[name]
+    m = conv_model(c["shape"]) if c["model"] == "conv8" else model_of(c["model"], c["shape"])
+    p = R.init_params(m, c["clf_seed"])
+    finite = [v if np.isfinite(v) else s for v, s in ((c["lo"], -1.0), (c["hi"], 1.0))]
+    if c["lo"] == c["hi"]:
+        finite = [-1.0, 1.0]                                        # the images of the signed range around the single point
+    x = sparse_images(c["B"], c["shape"], c["x_seed"], *finite) if c["sparse"] else images(c["B"], c["shape"], c["x_seed"])
+    if c["outside"]:
+        for i, at in enumerate(((3, 11, 20), (5, 17, 26))):
+            x[i].reshape(-1)[list(at)] = (1.5, -0.5, 1.5)
+    return m, p, x, targets(m, p, x, c["t_seed"])
+
+
+def edge_run(name):
+    """The float64 run of an EDGE_CASES entry with its float32 shadow, computed once and shared (never modified)."""
+    if ("edge", name) not in _RUNS:
+        c = EDGE_CASES[name]
+        m, p, x, t = edge_inputs(name)
+        _RUNS[("edge", name)] = run(m, p, x, t, c["theta"], c["max_iters"], c["lo"], c["hi"], bool(c["of_probs"]), shadow=torch.float32)
+    return _RUNS[("edge", name)]
+
+
+# 6. an infinite pixel: three classes on 4 x 4, dyadic weights none of which is zero (0 x inf would be a NaN logit), no bias.  Feature 5's
+# row is (1, -2, 3) / 8, so +inf there makes the logits (inf, -inf, inf) -- the first arg-max is class 0, the target 2 ties with it and
+# does not count -- and -inf makes them (-inf, inf, -inf).  theta has the pixel's sign, so the pixel is outside the domain, the logits
+# stay infinite for the whole run and the dyadic pair rule is an exact oracle for that image.
+INF_PIXEL = (1, 5)                   # image, feature
+INF_ITERS = 4
+
+
+def inf_case(sign):
+    """(model, params, x with the pixel at sign * inf, x without, target, theta)."""
+    rs = np.random.RandomState(41)
+    k = rs.randint(1, 4, (16, 3)) * rs.choice([-1, 1], (16, 3))
+    k[INF_PIXEL[1]] = (1, -2, 3)
+    x = images(4, (4, 4, 1), 42)
+    bad = x.copy()
+    bad[INF_PIXEL[0]].reshape(-1)[INF_PIXEL[1]] = sign * INF
+    return (model_of("lin3", (4, 4, 1)), [((k / 8.0).astype(np.float32), np.zeros(3, np.float32))], bad, x, np.full(4, 2, np.int32),
+            float(sign))
+
+
+# 8. the early exit: a linear model on 4 x 4 over 64 images; the batches are the images the float64 run finishes in exactly 1 and 2 steps
+EXIT_CASE = _case("lin5", (4, 4, 1), 64, of_probs=0, clf_seed=11, x_seed=2, max_iters=5)
+
+
+def exit_batches():
+    """(model, params, x, target, ref, {1: indices, 2: indices}): the decidable images of EXIT_CASE that reach their target after
+    exactly 1 and exactly 2 steps."""
+    m, p, x, t = case_inputs(EXIT_CASE)
+    ref = case_run(EXIT_CASE)
+    dec = decidable(ref)
+    done = ref["final_class"] == ref["target"]
+    return m, p, x, t, ref, {k: np.flatnonzero(dec & done & (ref["iters"] == k)) for k in (1, 2)}
